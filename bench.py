@@ -20,8 +20,13 @@ all_gather of the per-block output sizes (the table a container writer needs), i
   --scaling strong ONE corpus (seed 8, --bytes in total) cut into contiguous block ranges (comprox_amd.shard.partition);
                    rank 0 receives every rank's packed payloads after the timed region, assembles the stream in block
                    order and hashes it.
-What was timed is checked: the round trip must reproduce the input (else the run FAILS), and the SHA-256 of the
-concatenated payloads is compared with the unmodified reference's (tests/golden/golden_scale.json) -> bytes_equal_golden.
+What was timed is checked: the round trip must reproduce the input (else the run FAILS).
+
+A plain run sets up, warms up, times --steps steps, writes --dump-outputs if asked and prints the result line. Everything
+else is behind --full: the SHA-256 of the concatenated payloads against the unmodified reference's
+(tests/golden/golden_scale.json) -> bytes_equal_golden (a mismatch FAILS the run), the roofline figure of the dominant
+kernel, and the side measurements with runs of their own (two steps in flight, end to end from host memory, the CPU
+paths), each of which --no-overlap / --no-e2e / --no-cpu leaves out again.
 """
 import argparse
 import hashlib
@@ -45,9 +50,13 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--bytes", type=int, default=0, help="uncompressed bytes per GPU (weak) or in total (strong); default 1e8 (enwik), 2^28 (markov)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end (host memory in, host memory out) measurement")
-    ap.add_argument("--no-overlap", action="store_true", help="skip the extra measurement with two steps in flight (encode of step i + 1 beside the decode of step i)")
+    ap.add_argument("--full", action="store_true", help="also: compare the packed bytes with the reference's (bytes_equal_golden), the roofline figure, "
+                                                        "and the side measurements (two steps in flight, end to end, CPU paths)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them produced (block sizes, packed payloads, decoded bytes) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU paths timed beside the GPU's")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the end-to-end (host memory in, host memory out) measurement")
+    ap.add_argument("--no-overlap", action="store_true", help="with --full: skip the extra measurement with two steps in flight (encode of step i + 1 beside the decode of step i)")
     ap.add_argument("--codec", choices=["rop", "rox", "rolz"], default="rop", help="comprop (default, the bench workload), comprox or comprolz block codec")
     ap.add_argument("--stage", choices=["full", "codec"], default="full", help="full: dictionary stage + codec (the reference's per-block path); codec: lzencode / lzdecode only")
     ap.add_argument("--workload", choices=["enwik", "enwik-hard", "markov"], default="enwik",
@@ -58,7 +67,10 @@ def parse_args(argv=None):
     ap.add_argument("--deadline", type=float, default=float(os.environ.get("CRBENCH_DEADLINE_S", "900")),
                     help="seconds after which a run that has not finished is given up: a rank exits non-zero by itself (watchdog), and the "
                          "parent of --gpus N kills its child job and prints an error line (0 = none)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def error_line(args, what: str) -> str:
@@ -628,13 +640,18 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
 
+    if args.dump_outputs:                               # before anything below reuses the buffers
+        b_last = (nbatch - 1) * NBB                     # several batches: the packed run and the decoded bytes of the last one
+        dump_outputs(args.dump_outputs, {"enc_size": d_enc_size[:nb], "packed": d_pack[:int(d_total[0].item())],
+                                         "decoded": d_dec[:n - b_last * BLOCK]}, rank, world)
+
     # ---- what was timed is checked: the round trip, the sizes, the bytes
     comp = int(d_enc_size[:nb].to(i64).sum().item())
     st1_bytes = int(d_len1[:nb].to(i64).sum().item()) if full else n
     if nbatch == 1:
         ok = bool(torch.equal(d_dec[:n], d_in)) and bool((d_dec_size[:nb] == d_in_size).all().item()) and int(d_total[1].item()) == 0
         ok = ok and comp == int(d_total[0].item())
-        packed = d_pack[:comp].cpu().numpy()
+        packed = d_pack[:comp].cpu().numpy() if args.full else None      # (for the hashes below)
     else:
         acc = d_acc.tolist()                            # of the last timed step
         ok = acc[0] == 0 and acc[2] == 0 and acc[1] == comp
@@ -659,7 +676,7 @@ def main():
             golden_equal = None if cut is None else (cut["size"] == sum(rank_bytes) and cut["sha256"] == h.hexdigest())
         else:
             send_to(d_pack[:max(1, comp)].contiguous(), 0)
-    elif args.workload == "markov" and first_index == 0 and nb >= 256 and file_n >= MARKOV_DIC_BYTES:
+    elif args.full and args.workload == "markov" and first_index == 0 and nb >= 256 and file_n >= MARKOV_DIC_BYTES:
         # config 5: blocks 0 .. 255 of the stream once more (untimed) against the unmodified reference's bytes for them
         try:
             mk = json.load(open(os.path.join(ROOT, "tests", "golden", "golden_scale.json")))["o2"]["markov2_first256"][f"{args.codec}/{args.stage}"]["cuts"]["full"]
@@ -752,7 +769,7 @@ def main():
                 "roundtrip_ok": ok2, "packed_bytes_equal_the_serial_steps": same2}
 
     overlap = None
-    if world == 1 and nbatch == 1 and not args.no_overlap and 0 < nb <= 4096:     # (a second set of encoder arenas: not beside the 15 259 blocks of config 3)
+    if args.full and world == 1 and nbatch == 1 and not args.no_overlap and 0 < nb <= 4096:     # (a second set of encoder arenas: not beside the 15 259 blocks of config 3)
         try:
             overlap = two_in_flight()
         except Exception as e:  # noqa: BLE001 — a side measurement must not take the line down
@@ -789,7 +806,7 @@ def main():
         traffic, traffic_src, traffic_when = None, None, None
         import glob
         want_cmd = f"--stage {args.stage}"
-        for tpath in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_traffic*.json")), reverse=True):
+        for tpath in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_traffic*.json")), reverse=True) if args.full else ():
             try:
                 tj = json.load(open(tpath))
             except (OSError, ValueError):
@@ -820,6 +837,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(ms_step, 3),
             "higher_is_better": True,
             "scaling": args.scaling,
@@ -849,16 +867,16 @@ def main():
             "ranks_equal_golden": ranks_equal_golden,
             "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(ach, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(ach / HBM_PEAK_GBS, 6), "traffic": traffic, "traffic_source": traffic_src, "traffic_measured_on": traffic_when,
-                         "algorithmic_bytes": algo},
+                         "algorithmic_bytes": algo} if args.full else None,
         }
         if overlap is not None:
             line["two_steps_in_flight"] = overlap
-        if world == 1 and host is not None and not args.no_e2e and nbatch == 1:
+        if args.full and world == 1 and host is not None and not args.no_e2e and nbatch == 1:
             try:
                 line["end_to_end"] = end_to_end(local, host, CODEC, dic_text, full)
             except Exception as e:  # noqa: BLE001 — a side measurement
                 line["end_to_end"] = {"error": repr(e)}
-        if not args.no_cpu and host is not None:
+        if args.full and not args.no_cpu and host is not None:
             try:
                 line["cpu_baseline"] = cpu_baseline(host, dic_text, args.codec, full)
                 # vs_baseline stays null (BASELINE.md holds no published number for this metric); the ratios to the CPU
@@ -946,6 +964,21 @@ def end_to_end(local, host, codec, dic_text, full, reps=3):
             "marks": "ms from the call's start to: input on the device, stages done, sizes exchanged, output allocated, run copied to the host",
             "path": "host numpy buffer (pageable) -> crgpu_multi_encode_blocks -> page-locked pool -> crgpu_multi_decode_blocks -> page-locked pool, one device, "
                     + ("dictionary stage + codec" if full else "codec stage") + "; wall clock of the two calls, best of %d" % reps}
+
+
+def dump_outputs(dirpath, tensors, rank, world, cap=1 << 22):
+    """--dump-outputs: every 1-D device tensor of `tensors` as DIR/<name>.npy (<name>_rank<r>.npy when there are several
+    ranks), float32 — exact for bytes and block sizes. A tensor of more than cap / world elements is cut down to that many
+    positions drawn with a fixed seed (sorted, the same for the same length), so that a run writes at most 3 x 16 MB and
+    two builds given the same arguments write arrays that compare element for element."""
+    import numpy as np
+    import torch
+    os.makedirs(dirpath, exist_ok=True)
+    for name, t in tensors.items():
+        if t.numel() > cap // world:
+            idx = np.sort(np.random.default_rng(0x5EED).integers(0, t.numel(), size=cap // world))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(dirpath, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), t.cpu().numpy().astype(np.float32))
 
 
 def host_dicpick(lib, data) -> bytes:

@@ -17,11 +17,36 @@ pytestmark = pytest.mark.gpu
 def run_bench(args, **more_env):
     env = dict(os.environ, CRBENCH_BACKEND="gloo", CRBENCH_ONE_GPU="1", **more_env)
     env.pop("RANK", None)
-    p = subprocess.run([sys.executable, os.path.join(crlib.ROOT, "bench.py")] + args, capture_output=True, text=True, env=env, timeout=900)
+    # --full: the comparison with the reference's bytes (bytes_equal_golden & co.) and the two steps in flight are not part of a plain run
+    p = subprocess.run([sys.executable, os.path.join(crlib.ROOT, "bench.py"), "--full"] + args, capture_output=True, text=True, env=env, timeout=900)
     assert p.returncode == 0, "\n".join(l for l in p.stderr.splitlines() if "rank" in l or "Error" in l)[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]
     return json.loads(lines[0])
+
+
+def test_plain_run_dumps_what_its_last_step_produced(tmp_path):
+    """A run without --full sets up, times --steps steps and prints the line: no comparison with the reference, no side
+    measurement. --dump-outputs writes the last step's block sizes, packed payloads and decoded bytes as float32 arrays:
+    here the 1 MiB cut of the bench corpus, whose packed bytes the unmodified reference pins (golden_scale.json)."""
+    import hashlib
+    import numpy as np
+    from comprox_amd import corpus
+    env = {k: v for k, v in os.environ.items() if k != "RANK"}
+    p = subprocess.run([sys.executable, os.path.join(crlib.ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--bytes", "1048576",
+                        "--stage", "codec", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, env=env, timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 - 1.048576) < 0.01 * 1.048576       # MB/s x s per step = the MB of one step (both rounded)
+    assert d["roundtrip_ok"] is True and d["full"] is False and d["bytes_equal_golden"] is None and d["roofline"] is None
+    assert not {"two_steps_in_flight", "end_to_end", "cpu_baseline"} & set(d)
+    arrays = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in sorted(os.listdir(tmp_path))}
+    assert sorted(arrays) == ["decoded", "enc_size", "packed"] and all(a.dtype == np.float32 for a in arrays.values())
+    cut = json.load(open(os.path.join(crlib.ROOT, "tests", "golden", "golden_scale.json")))["o2"]["enwik_like_1e8_seed8"]["rop/codec"]["cuts"]["1MiB"]
+    assert arrays["enc_size"].size == 16 and int(arrays["enc_size"].sum()) == cut["size"] == arrays["packed"].size
+    assert hashlib.sha256(arrays["packed"].astype(np.uint8).tobytes()).hexdigest() == cut["sha256"]
+    assert np.array_equal(arrays["decoded"].astype(np.uint8), corpus.enwik_like(1048576, seed=8))
 
 
 def test_two_ranks_strong_scaling_assembles_the_reference_stream():

@@ -13,7 +13,7 @@ mkdir -p $O
 run_cfg() {   # name, bench arguments
   local name=$1; shift
   echo "== $name: $*"
-  (cd $R && timeout -k 10 900 python3 bench.py --no-cpu --no-e2e --no-overlap --steps 3 --warmup 1 "$@" > $O/bench_line_$name.json 2>> $O/err_$name.txt) || { tail -5 $O/err_$name.txt; return 1; }
+  (cd $R && timeout -k 10 900 python3 bench.py --full --no-cpu --no-e2e --no-overlap --steps 3 --warmup 1 "$@" > $O/bench_line_$name.json 2>> $O/err_$name.txt) || { tail -5 $O/err_$name.txt; return 1; }
   python3 -c "import json,sys; d=json.load(open('$O/bench_line_$name.json')); print(d['value'], d['ms_per_step'], d['roundtrip_ok'], d['bytes_equal_golden'])"
   bash $R/tools/sq_counters.sh $TAG/sq_$name "$@" > /dev/null 2>> $O/err_$name.txt
   cp $O/sq_$name/sq_counters.txt $O/sq_counters_$name.txt

@@ -7,9 +7,9 @@ TAG=${1:-r02a}
 CODECS=${2:-rop rox rolz}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
-timeout -k 10 600 python bench.py > $O/bench_line_rop.json 2> $O/bench_err.txt
+timeout -k 10 600 python bench.py --full > $O/bench_line_rop.json 2> $O/bench_err.txt
 tail -c 2500 $O/bench_line_rop.json; echo
-timeout -k 10 300 python bench.py --stage codec --no-cpu > $O/bench_line_rop_codec.json 2>> $O/bench_err.txt
+timeout -k 10 300 python bench.py --full --stage codec --no-cpu > $O/bench_line_rop_codec.json 2>> $O/bench_err.txt
 cd /tmp && export TMPDIR=/tmp
 for c in $CODECS; do
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$c -- python3 $R/bench.py --no-cpu --no-e2e --no-overlap --codec $c > $O/bench_under_rocprof_$c.json 2>/dev/null
@@ -22,7 +22,7 @@ for c in $CODECS; do
     rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write_${c}_codec -- python3 $R/bench.py --steps 1 --warmup 1 --no-cpu --no-e2e --no-overlap --codec $c --stage codec > /dev/null 2>&1
     (cd $R && python3 tools/collect_traffic.py gpurun_out/$TAG/pmc_fetch_${c}_codec gpurun_out/$TAG/pmc_write_${c}_codec gpurun_out/$TAG/traffic_${c}_codec.json "--steps 1 --warmup 1 --no-cpu --codec $c --stage codec" > /dev/null)
   fi
-  if [ $c != rop ]; then timeout -k 10 300 python3 $R/bench.py --no-cpu --codec $c > $O/bench_line_$c.json 2>> $O/bench_err.txt; fi
+  if [ $c != rop ]; then timeout -k 10 300 python3 $R/bench.py --full --no-cpu --codec $c > $O/bench_line_$c.json 2>> $O/bench_err.txt; fi
   head -14 $O/kernel_stats_$c.csv | cut -c1-110
 done
 cd $R

@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/${1:-ovt}
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $O/trace -- python3 $R/bench.py --steps 4 --warmup 1 --no-cpu --no-e2e ${2:+--codec $2} > $O/line.json 2> $O/err.txt
+rocprofv3 --kernel-trace --output-format csv -d $O/trace -- python3 $R/bench.py --full --steps 4 --warmup 1 --no-cpu --no-e2e ${2:+--codec $2} > $O/line.json 2> $O/err.txt
 cd $R
 python3 - <<PY
 import csv, glob

@@ -13,9 +13,9 @@ mkdir -p "$O"
 avail=$(python3 -c "import torch; print(torch.cuda.device_count())")
 for n in $G; do
   if [ "$n" -gt "$avail" ]; then echo "skipping N=$n: $avail GPU(s) on this box"; continue; fi
-  timeout -k 10 900 python3 bench.py --gpus $n --no-cpu --no-e2e > $O/weak_n$n.json 2> $O/weak_n$n.err || echo "weak N=$n failed (see $O/weak_n$n.err)"
-  timeout -k 10 900 python3 bench.py --gpus $n --no-cpu --no-e2e --scaling strong > $O/strong_1e8_n$n.json 2> $O/strong_1e8_n$n.err || echo "strong 1e8 N=$n failed"
-  timeout -k 10 1500 python3 bench.py --gpus $n --no-cpu --no-e2e --scaling strong --bytes 1000000000 --steps 2 --warmup 1 > $O/strong_1e9_n$n.json 2> $O/strong_1e9_n$n.err || echo "strong 1e9 N=$n failed"
+  timeout -k 10 900 python3 bench.py --full --gpus $n --no-cpu --no-e2e > $O/weak_n$n.json 2> $O/weak_n$n.err || echo "weak N=$n failed (see $O/weak_n$n.err)"
+  timeout -k 10 900 python3 bench.py --full --gpus $n --no-cpu --no-e2e --scaling strong > $O/strong_1e8_n$n.json 2> $O/strong_1e8_n$n.err || echo "strong 1e8 N=$n failed"
+  timeout -k 10 1500 python3 bench.py --full --gpus $n --no-cpu --no-e2e --scaling strong --bytes 1000000000 --steps 2 --warmup 1 > $O/strong_1e9_n$n.json 2> $O/strong_1e9_n$n.err || echo "strong 1e9 N=$n failed"
 done
 python3 - "$O" <<'PY'
 import glob, json, os, sys
