@@ -22,6 +22,7 @@ OPT_LZP_TABLES = 6
 OPT_STAGE_LOG = 7
 OPT_DECODER_HELPER = 8
 OPT_DECODER_LDS_NODES = 9
+OPT_DICPICK_EPOCHS = 10
 _HEADER = {CODEC_ROP: 20, CODEC_ROX: 32, CODEC_ROLZ: 16}
 
 _LIB = None
@@ -34,6 +35,12 @@ class CrGpuError(RuntimeError):
 class DataBlock(ctypes.Structure):
     """data_block_t (reference src/cr-datablock.h:35-39)."""
     _fields_ = [("m_data", ctypes.c_void_p), ("m_size", ctypes.c_uint32), ("m_capacity", ctypes.c_uint32)]
+
+
+class DicpickInfo(ctypes.Structure):
+    """crgpu_dicpick_info."""
+    _fields_ = [("tokens", ctypes.c_uint32), ("distinct", ctypes.c_uint32), ("purges", ctypes.c_uint32),
+                ("fell_back", ctypes.c_uint32), ("kernel_ms", ctypes.c_float)]
 
 
 def library_path() -> str:
@@ -96,6 +103,12 @@ def load_library():
     L.crgpu_dict_encode_blocks_dev.argtypes = [vp, vp, vp, vp, vp, u32, u32, vp, vp, vp, i32]
     L.crgpu_dict_decode_blocks_dev.restype = i32
     L.crgpu_dict_decode_blocks_dev.argtypes = [vp, vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, i32]
+    L.crgpu_dicpick_dev.restype = i32
+    L.crgpu_dicpick_dev.argtypes = [vp, vp, ctypes.c_uint64, ctypes.POINTER(DataBlock), ctypes.POINTER(DicpickInfo)]
+    L.crgpu_dicpick.restype = i32
+    L.crgpu_dicpick.argtypes = [vp, vp, ctypes.c_uint64, ctypes.POINTER(DataBlock), ctypes.POINTER(DicpickInfo)]
+    L.data_block_destroy.restype = None
+    L.data_block_destroy.argtypes = [ctypes.POINTER(DataBlock)]
     L.crgpu_selftest.restype = i32
     L.crgpu_selftest.argtypes = [vp, vp, vp]
     L.crgpu_debug_stats.restype = i32
@@ -299,6 +312,24 @@ class CrGpu:
     # ---- static-dictionary stage ----------------------------------------------------
     def dict_create(self, text: bytes) -> "CrDict":
         return CrDict(self, text)
+
+    def _dicpick(self, fn, what, src, n):
+        db, info = DataBlock(), DicpickInfo()
+        rc = fn(self.h, src, n, ctypes.byref(db), ctypes.byref(info))
+        text = ctypes.string_at(db.m_data, db.m_size) if db.m_data else b""
+        self.lib.data_block_destroy(ctypes.byref(db))
+        self._check(rc, what)
+        return text, {"tokens": info.tokens, "distinct": info.distinct, "purges": info.purges,
+                      "fell_back": info.fell_back, "kernel_ms": info.kernel_ms}
+
+    def dicpick_dev(self, d_src: int, n: int):
+        """crgpu_dicpick_dev: dicpick() of the n bytes at device pointer d_src -> (dictionary text, info dict)."""
+        return self._dicpick(self.lib.crgpu_dicpick_dev, "crgpu_dicpick_dev", ctypes.c_void_p(d_src), n)
+
+    def dicpick(self, data):
+        """crgpu_dicpick: the same for host bytes."""
+        src = np.frombuffer(bytes(data) or b"\0", dtype=np.uint8)
+        return self._dicpick(self.lib.crgpu_dicpick, "crgpu_dicpick", _ptr(src), len(data))
 
     def selftest(self, values, limit, index):
         inp = np.zeros(66, dtype=np.uint32)

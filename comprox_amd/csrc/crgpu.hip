@@ -28,6 +28,7 @@
 #include "crgpu_links2.h"
 #include "crgpu_rolz3.h"
 #include "crgpu_rox3.h"
+#include "crgpu_dicpick.h"
 
 /* ------------------------------------------------------------------ kernels */
 
@@ -947,6 +948,9 @@ struct crgpu_ctx {
     uint8_t*    d_rox; size_t d_rox_cap;        /* comprox encode: per-position match tables */
     uint8_t*    d_ev; size_t d_ev_cap;          /* comprop chain encoder: per-block event scratch */
     uint8_t*    d_side; size_t d_side_cap;      /* comprox chain encoder: per-block side-stream staging */
+    uint8_t*    d_dic_tiles; size_t d_dic_tiles_cap;   /* crgpu_dicpick_dev: state words + per-tile token counts */
+    uint8_t*    d_dic; size_t d_dic_cap;               /* crgpu_dicpick_dev: tokens, slot ids, table, hits */
+    uint32_t    dic_epochs;                     /* CRGPU_OPT_DICPICK_EPOCHS: purges replayed on the device before the host census takes over */
     int         one_wave_encoder;   /* CRGPU_OPT_ONE_WAVE_ENCODER: the model-carrying one-wave coders instead of the kernel pipeline */
     int         one_wave_decoder;   /* CRGPU_OPT_ONE_WAVE_DECODER: the model-carrying C++ decoders instead of the assembly step */
     uint32_t    lzp_grid, match_grid;   /* experiments: at most this many workgroups for the pre-pass kernels (0 = no limit) */
@@ -1117,6 +1121,7 @@ extern "C" int crgpu_create(crgpu_ctx** out, int device) {
     }
     c->stream = c->own_stream;
     c->rox_limit = CR_ROX_LIMIT;
+    c->dic_epochs = 256;
     /* diagnostic switches: the environment is read HERE, once; crgpu_set_option changes them on a live context */
     static const struct { const char* env; int opt; } k_env[] = {
         {"CRGPU_WG_PER_CU", CRGPU_OPT_WG_PER_CU}, {"CRGPU_ONE_WAVE_ENCODER", CRGPU_OPT_ONE_WAVE_ENCODER},
@@ -1142,6 +1147,7 @@ extern "C" int crgpu_set_option(crgpu_ctx* c, int option, int value) {
         case CRGPU_OPT_LZP_TABLES:       c->lzp_tables_only = value != 0; return CRGPU_OK;
         case CRGPU_OPT_DECODER_HELPER:   c->decoder_helper = value != 0; return CRGPU_OK;
         case CRGPU_OPT_DECODER_LDS_NODES: c->decoder_small_lds = value == 0; return CRGPU_OK;
+        case CRGPU_OPT_DICPICK_EPOCHS:   c->dic_epochs = (uint32_t)value; return CRGPU_OK;
         case CRGPU_OPT_STAGE_LOG:
             /* events of the pool may still be pending on the stream: let them pass before the pool is handed out again */
             if (c->pool_used && (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)) return CRGPU_E_NODEVICE;
@@ -1156,7 +1162,7 @@ extern "C" void crgpu_destroy(crgpu_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    for (int i = 0; i < 3; i++) (void)hipFree(c->arenas[i].p); (void)hipFree(c->ticket); (void)hipFree(c->d_in); (void)hipFree(c->d_out); (void)hipFree(c->d_meta); (void)hipFree(c->d_lens); (void)hipFree(c->d_done); (void)hipFree(c->d_rox); (void)hipFree(c->d_ev); (void)hipFree(c->d_side); (void)hipEventDestroy(c->ev_mid); for (int i = 0; i <= CRGPU_MAX_STAGES; i++) if (c->ev_own[i]) (void)hipEventDestroy(c->ev_own[i]);
+    for (int i = 0; i < 3; i++) (void)hipFree(c->arenas[i].p); (void)hipFree(c->ticket); (void)hipFree(c->d_in); (void)hipFree(c->d_out); (void)hipFree(c->d_meta); (void)hipFree(c->d_lens); (void)hipFree(c->d_done); (void)hipFree(c->d_rox); (void)hipFree(c->d_ev); (void)hipFree(c->d_side); (void)hipFree(c->d_dic_tiles); (void)hipFree(c->d_dic); (void)hipEventDestroy(c->ev_mid); for (int i = 0; i <= CRGPU_MAX_STAGES; i++) if (c->ev_own[i]) (void)hipEventDestroy(c->ev_own[i]);
     for (int i = 0; i < c->pool_n; i++) (void)hipEventDestroy(c->pool[i]);
     free(c->pool); free(c->log);
     (void)hipEventDestroy(c->ev0); (void)hipEventDestroy(c->ev1);
@@ -1914,6 +1920,168 @@ extern "C" int crgpu_dict_decode_blocks(crgpu_ctx* c, crgpu_dict* d, const uint8
                                         const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_size) {
     if (!d) return CRGPU_E_ARG;
     return host_call(c, 0, d, 1, in, in_off, in_size, nblocks, out, out_off, out_cap, out_size);
+}
+
+/* ------------------------------------------------------------------ dictionary pick on the device (crgpu_dicpick.h) */
+
+/* The census is several groups of kernels with a readback between them; every group goes to the stage log on its own. */
+static int dic_group_open(crgpu_ctx* c) { c->n_stages = 0; return stage_begin(c); }
+static int dic_group_close(crgpu_ctx* c) {
+    CR_TRY(c, hipEventRecord(c->ev_stage[c->n_stages], c->stream));
+    return stage_end(c);
+}
+#define CR_DIC_STAGE(name_, kernel_, grid_, threads_, ...) do { \
+        if (c->n_stages >= CRGPU_MAX_STAGES) { snprintf(c->err, sizeof c->err, "internal: more than %d kernels in one group", CRGPU_MAX_STAGES); return CRGPU_E_ARG; } \
+        CR_TRY(c, hipEventRecord(c->ev_stage[c->n_stages], c->stream)); \
+        hipLaunchKernelGGL(kernel_, dim3(grid_), dim3(threads_), 0, c->stream, __VA_ARGS__); \
+        CR_TRY(c, hipGetLastError()); \
+        c->stage_name[c->n_stages++] = name_; \
+    } while (0)
+#define CR_DIC_RC(call_) do { const int rc_ = (call_); if (rc_ != CRGPU_OK) return rc_; } while (0)
+
+static int dic_read_state(crgpu_ctx* c, const CrDic& D, uint32_t* st) {
+    CR_TRY(c, hipMemcpyAsync(st, D.st, sizeof(uint32_t) * CR_DS_WORDS, hipMemcpyDeviceToHost, c->stream));
+    CR_TRY(c, hipStreamSynchronize(c->stream));
+    return CRGPU_OK;
+}
+
+static uint32_t dic_blocks(u64 items, uint32_t per) { return (uint32_t)((items + per - 1u) / per); }
+
+/* The purge of cr-dicpick.c:115-144 replayed in epochs (crgpu_dicpick.h); hits are counted afresh. *live = the words in
+ * the map at the stream's end. Gives up (*gave_up = 1) when the context's cap of purges is reached. */
+static int dic_replay(crgpu_ctx* c, CrDic& D, uint32_t* purges, uint32_t* live, int* gave_up) {
+    const uint32_t slot_grid = dic_blocks(D.nslots, CR_DIC_THREADS) < (uint32_t)c->num_cu * 8u ? dic_blocks(D.nslots, CR_DIC_THREADS) : (uint32_t)c->num_cu * 8u;
+    uint32_t st[CR_DS_WORDS];
+    CR_DIC_RC(dic_group_open(c));
+    CR_DIC_STAGE("k_dic_fill32", k_dic_fill32, slot_grid, CR_DIC_THREADS, D.hits, D.nslots, 0u);
+    CR_DIC_STAGE("k_dic_fill32", k_dic_fill32, slot_grid, CR_DIC_THREADS, D.first, D.nslots, 0xFFFFFFFFu);
+    CR_DIC_RC(dic_group_close(c));
+    for (uint32_t from = 0;;) {
+        if (*purges >= c->dic_epochs) { *gave_up = 1; return CRGPU_OK; }
+        const uint32_t rest = D.ntok - from, nblk = dic_blocks(rest, CR_DIC_BLK);
+        CR_DIC_RC(dic_group_open(c));
+        if (rest) {
+            CR_DIC_STAGE("k_dic_first", k_dic_first, dic_blocks(rest, CR_DIC_THREADS), CR_DIC_THREADS, D, from);
+            CR_DIC_STAGE("k_dic_flags", k_dic_flags, nblk, CR_DIC_BLK, D, from);
+        }
+        CR_DIC_STAGE("k_dic_select", k_dic_select, 1, CR_DIC_BLK, D, from, nblk);
+        CR_DIC_RC(dic_read_state(c, D, st));
+        if (!st[CR_DS_FOUND]) {                                  /* no further purge: the rest of the stream is counted */
+            if (rest) CR_DIC_STAGE("k_dic_count", k_dic_count, dic_blocks(rest, CR_DIC_THREADS), CR_DIC_THREADS, D, from, D.ntok - 1u);
+            CR_DIC_RC(dic_group_close(c));
+            *live = st[CR_DS_LIVE_WAS] + st[CR_DS_NEW];
+            return CRGPU_OK;
+        }
+        const uint32_t point = st[CR_DS_POINT];
+        CR_DIC_STAGE("k_dic_count", k_dic_count, dic_blocks((u64)point - from + 1u, CR_DIC_THREADS), CR_DIC_THREADS, D, from, point);
+        CR_DIC_STAGE("k_dic_min", k_dic_min, slot_grid, CR_DIC_THREADS, D);
+        CR_DIC_STAGE("k_dic_purge", k_dic_purge, slot_grid, CR_DIC_THREADS, D);
+        CR_DIC_RC(dic_group_close(c));
+        *purges += 1u;
+        from = point + 1u;
+    }
+}
+
+/* more purges than the device replays: the stream goes to the host and through dicpick() */
+static int dic_host_census(crgpu_ctx* c, const uint8_t* dev_src, u64 n, data_block_t* dic_block) {
+    uint8_t* h = (uint8_t*)malloc((size_t)n);
+    if (!h) { snprintf(c->err, sizeof c->err, "malloc(%llu) failed", n); return CRGPU_E_NOMEM; }
+    hipError_t e = hipMemcpyAsync(h, dev_src, (size_t)n, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    FILE* fp = e == hipSuccess ? fmemopen(h, (size_t)n, "rb") : NULL;
+    if (fp) { dicpick(fp, dic_block); fclose(fp); }
+    free(h);
+    if (e != hipSuccess) return fail(c, e, "hipMemcpyAsync(stream to host)");
+    if (!fp) { snprintf(c->err, sizeof c->err, "fmemopen failed"); return CRGPU_E_NOMEM; }
+    return CRGPU_OK;
+}
+
+extern "C" int crgpu_dicpick_dev(crgpu_ctx* c, const uint8_t* dev_src, uint64_t n, data_block_t* dic_block, crgpu_dicpick_info* info) {
+    if (!c || !dic_block || (n && !dev_src)) return CRGPU_E_ARG;
+    if (n > 0xFFFFFFFFull) { snprintf(c->err, sizeof c->err, "stream of %llu bytes exceeds 2^32 - 1", (u64)n); return CRGPU_E_ARG; }
+    CR_TRY(c, hipSetDevice(c->device));
+    crgpu_dicpick_info I;
+    memset(&I, 0, sizeof I);
+    CrDic D;
+    memset(&D, 0, sizeof D);
+    D.src = dev_src; D.n = n; D.ntiles = dic_blocks(n, CR_DIC_TILE);
+    uint32_t st[CR_DS_WORDS] = {0}, live = 0, kept = 0;
+    int gave_up = 0;
+    CR_TRY(c, hipEventRecord(c->ev0, c->stream));
+    CR_TRY(c, hipEventRecord(c->ev_mid, c->stream));
+    if (D.ntiles) {
+        CR_DIC_RC(grow(c, &c->d_dic_tiles, &c->d_dic_tiles_cap, 256u + 4u * (size_t)D.ntiles));
+        D.st = (uint32_t*)c->d_dic_tiles; D.tile_cnt = D.st + 64;
+        CR_TRY(c, hipMemsetAsync(D.st, 0, 256, c->stream));
+        CR_DIC_RC(dic_group_open(c));
+        CR_DIC_STAGE("k_dic_scan_count", k_dic_scan<false>, D.ntiles, CR_DIC_THREADS, D);
+        CR_DIC_STAGE("k_dic_offsets", k_dic_offsets, 1, CR_DIC_BLK, D);
+        CR_DIC_RC(dic_group_close(c));
+        CR_DIC_RC(dic_read_state(c, D, st));
+        D.ntok = st[CR_DS_TOKENS];
+    }
+    if (D.ntok) {
+        /* 8 ntok (tokens; later the replay's first[], then the kept cells: at most ntok / 6 words have 6 hits) + 4 ntok (slot
+         * ids) + 12 per slot (table, hits) with 1.5 slots per token: 30 bytes per token */
+        D.nslots = D.ntok + D.ntok / 2u < 1024u ? 1024u : D.ntok + D.ntok / 2u;
+        u64 shared = 8ull * D.ntok;
+        if (shared < 4ull * D.nslots) shared = 4ull * D.nslots;
+        if (shared < sizeof(crh_cell) * ((u64)D.ntok / 6u + 1u)) shared = sizeof(crh_cell) * ((u64)D.ntok / 6u + 1u);
+        const u64 o_slot = align_up(shared, 256), o_table = align_up(o_slot + 4ull * D.ntok, 256), o_hits = o_table + 8ull * D.nslots;
+        const u64 o_blk = align_up(o_hits + 4ull * D.nslots, 256), total = o_blk + 4ull * dic_blocks(D.ntok, CR_DIC_BLK);
+        CR_DIC_RC(grow(c, &c->d_dic, &c->d_dic_cap, (size_t)total));
+        D.toks = (CrDicTok*)c->d_dic; D.first = (uint32_t*)c->d_dic; D.cells = (crh_cell*)c->d_dic;
+        D.slot_of = (uint32_t*)(c->d_dic + o_slot); D.table = (u64*)(c->d_dic + o_table);
+        D.hits = (uint32_t*)(c->d_dic + o_hits); D.blk_cnt = (uint32_t*)(c->d_dic + o_blk);
+        CR_TRY(c, hipMemsetAsync(D.table, 0, (size_t)(12ull * D.nslots), c->stream));
+        CR_DIC_RC(dic_group_open(c));
+        CR_DIC_STAGE("k_dic_scan_fill", k_dic_scan<true>, D.ntiles, CR_DIC_THREADS, D);
+        CR_DIC_STAGE("k_dic_insert", k_dic_insert, dic_blocks(D.ntok, CR_DIC_THREADS), CR_DIC_THREADS, D);
+        CR_DIC_RC(dic_group_close(c));
+        CR_DIC_RC(dic_read_state(c, D, st));
+        I.tokens = D.ntok; I.distinct = live = st[CR_DS_DISTINCT];
+        /* fewer different words than the map holds: it never purged and the totals are the census */
+        if (I.distinct >= CR_DIC_FULL) CR_DIC_RC(dic_replay(c, D, &I.purges, &live, &gave_up));
+        if (!gave_up) {
+            const uint32_t grid = dic_blocks(D.nslots, CR_DIC_THREADS) < (uint32_t)c->num_cu * 8u ? dic_blocks(D.nslots, CR_DIC_THREADS) : (uint32_t)c->num_cu * 8u;
+            CR_DIC_RC(dic_group_open(c));
+            CR_DIC_STAGE("k_dic_keep", k_dic_keep, grid, CR_DIC_THREADS, D);
+            CR_DIC_RC(dic_group_close(c));
+            CR_DIC_RC(dic_read_state(c, D, st));
+            kept = st[CR_DS_KEPT];
+        }
+    }
+    CR_TRY(c, hipEventRecord(c->ev1, c->stream));
+    c->timed = 1;
+    if (gave_up) {
+        I.fell_back = 1;
+        CR_DIC_RC(dic_host_census(c, dev_src, n, dic_block));
+    } else {
+        crh_cell* cells = (crh_cell*)malloc(sizeof(crh_cell) * ((size_t)kept + 1u));
+        if (!cells) { snprintf(c->err, sizeof c->err, "malloc(%u cells) failed", kept); return CRGPU_E_NOMEM; }
+        hipError_t e = kept ? hipMemcpyAsync(cells, D.cells, sizeof(crh_cell) * (size_t)kept, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) { free(cells); return fail(c, e, "hipMemcpyAsync(kept words)"); }
+        crh_dict_tail(cells, (int)kept, (int)live, dic_block);
+        free(cells);
+    }
+    if (info) {
+        CR_TRY(c, hipEventSynchronize(c->ev1));
+        CR_TRY(c, hipEventElapsedTime(&I.kernel_ms, c->ev0, c->ev1));
+        *info = I;
+    }
+    return CRGPU_OK;
+}
+
+extern "C" int crgpu_dicpick(crgpu_ctx* c, const uint8_t* host_src, uint64_t n, data_block_t* dic_block, crgpu_dicpick_info* info) {
+    if (!c || !dic_block || (n && !host_src)) return CRGPU_E_ARG;
+    if (n > 0xFFFFFFFFull) { snprintf(c->err, sizeof c->err, "stream of %llu bytes exceeds 2^32 - 1", (u64)n); return CRGPU_E_ARG; }
+    CR_TRY(c, hipSetDevice(c->device));
+    if (n) {
+        CR_DIC_RC(grow(c, &c->d_in, &c->d_in_cap, (size_t)n));
+        CR_TRY(c, hipMemcpyAsync(c->d_in, host_src, (size_t)n, hipMemcpyHostToDevice, c->stream));
+    }
+    return crgpu_dicpick_dev(c, c->d_in, n, dic_block, info);
 }
 
 /* wave-primitive self test: in = 66 u32 (64 lane values, mask limit, table index), out = 384 u32 */

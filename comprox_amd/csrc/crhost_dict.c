@@ -14,6 +14,7 @@
 #include <string.h>
 
 #include "../../include/crgpu.h"
+#include "crgpu_dicpick.h"                                 /* crh_cell, crh_dict_tail: shared with the device census */
 
 #define CRH_MAXWORDS   25000                               /* cr-diccode.h:39 */
 #define CRH_LEVEL1(n)  ((65535 - (int)(n)) / 255 - 1)      /* cr-diccode.h:40 */
@@ -23,8 +24,6 @@
 #define CRH_MAP_SLOTS  (CRH_MAXWORDS * 23 + 3)             /* cr-dicpick.c:34 */
 #define CRH_KEEP_ABOVE 5                                   /* cr-dicpick.c:35 */
 #define CRH_CHUNK      200000                              /* cr-dicpick.c:162 */
-
-typedef struct { char text[CRH_WORD_MAX + 1]; int hits; } crh_cell;
 
 /* The reference classifies bytes with isalpha / islower / tolower and never calls setlocale, i.e. in the "C" locale:
  * ASCII letters only. The census looks at every byte of the file, so the classes are table lookups here (bit 0 letter,
@@ -100,6 +99,29 @@ static int crh_by_text(const void* pa, const void* pb) {   /* cr-dicpick.c:53-57
     return strcmp(((const crh_cell*)pa)->text, ((const crh_cell*)pb)->text);
 }
 
+/* cr-dicpick.c:227-257, for the host census below and the device census (crgpu_dicpick_dev) alike */
+void crh_dict_tail(crh_cell* cells, int kept, int live, data_block_t* dic_block) {
+    qsort(cells, (size_t)kept, sizeof(crh_cell), crh_by_hits);
+    const char* reserved[2] = {"\x20\x20", "http://www."}; /* cr-dicpick.c:38-41 */
+    const int nres = 2;
+    if (kept > CRH_MAXWORDS - nres) kept = CRH_MAXWORDS - nres;
+    if (kept > CRH_LEVEL1(kept) - nres) {                  /* words with 2-byte codes go in name order */
+        int first = CRH_LEVEL1(kept) - nres;
+        qsort(cells + first, (size_t)(kept - first), sizeof(crh_cell), crh_by_text);
+    }
+    data_block_reserve(dic_block, (uint32_t)((live + nres) * (CRH_WORD_MAX + 3)));
+    for (int r = 0; r < nres; r++) {
+        for (const char* p = reserved[r]; *p; p++) data_block_add(dic_block, (uint8_t)*p);
+        data_block_add(dic_block, '\n');
+    }
+    for (int i = 0; i < kept; i++) {
+        if (i >= CRH_LEVEL1(kept) && strlen(cells[i].text) < CRH_WORD_MIN + 1) continue;   /* cr-dicpick.c:254 */
+        for (const char* p = cells[i].text; *p; p++) data_block_add(dic_block, (uint8_t)*p);
+        data_block_add(dic_block, '\n');
+    }
+    data_block_add(dic_block, 0);
+}
+
 /* dicpick(), cr-dicpick.c:164-273: reads `fp` to its end in 200 000-byte chunks */
 void dicpick(FILE* fp, data_block_t* dic_block) {
     crh_cell* map = (crh_cell*)calloc(CRH_MAP_SLOTS, sizeof(crh_cell));
@@ -151,25 +173,7 @@ void dicpick(FILE* fp, data_block_t* dic_block) {
             kept++;
         }
     }
-    qsort(map, (size_t)kept, sizeof(crh_cell), crh_by_hits);
-    const char* reserved[2] = {"\x20\x20", "http://www."}; /* cr-dicpick.c:38-41 */
-    const int nres = 2;
-    if (kept > CRH_MAXWORDS - nres) kept = CRH_MAXWORDS - nres;
-    if (kept > CRH_LEVEL1(kept) - nres) {                  /* words with 2-byte codes go in name order */
-        int first = CRH_LEVEL1(kept) - nres;
-        qsort(map + first, (size_t)(kept - first), sizeof(crh_cell), crh_by_text);
-    }
-    data_block_reserve(dic_block, (uint32_t)((live + nres) * (CRH_WORD_MAX + 3)));
-    for (int r = 0; r < nres; r++) {
-        for (const char* p = reserved[r]; *p; p++) data_block_add(dic_block, (uint8_t)*p);
-        data_block_add(dic_block, '\n');
-    }
-    for (int i = 0; i < kept; i++) {
-        if (i >= CRH_LEVEL1(kept) && strlen(map[i].text) < CRH_WORD_MIN + 1) continue;   /* cr-dicpick.c:254 */
-        for (const char* p = map[i].text; *p; p++) data_block_add(dic_block, (uint8_t)*p);
-        data_block_add(dic_block, '\n');
-    }
-    data_block_add(dic_block, 0);
+    crh_dict_tail(map, kept, live, dic_block);
     free(buf);
     free(map);
 }

@@ -88,6 +88,8 @@ int  crgpu_set_stream(crgpu_ctx* ctx, void* hip_stream);
                                           (k_rop_decode_v5, 8.7 KB of LDS per block in flight); 0: k_rop_decode_v5s, 272 bytes — for a
                                           caller that runs another context's encode calls beside this one's decodes, so that the
                                           decoder's workgroups leave room on a CU for a sorting kernel's 152 KB. Same bytes          */
+#define CRGPU_OPT_DICPICK_EPOCHS    10   /* crgpu_dicpick_dev: purges of the reference's word map replayed on the device before the
+                                          stream goes to the host census instead (default 256; 0: always the host census)  */
 int  crgpu_set_option(crgpu_ctx* ctx, int option, int value);
 
 /*
@@ -321,6 +323,19 @@ void dictionary_decode(data_block_t* i_block, data_block_t* o_block, FILE* fpout
 void dicpick(FILE* fp, data_block_t* dic_block);
 void dic_lcp_encode(data_block_t* dic_block);
 void dic_lcp_decode(data_block_t* dic_block);
+
+/* dicpick() for a stream that lies in device memory: the word census of src/cr-dicpick.c:164-226 as HIP kernels
+ * (csrc/crgpu_dicpick.h) on the context's stream, the tail (:227-257) on the host over the kept words. dic_block receives
+ * exactly the bytes dicpick() appends for a file holding the same n bytes; n <= 2^32 - 1 (CRGPU_E_ARG above). The call
+ * returns when dic_block is complete. info (may be NULL): tokens = words counted, distinct = different words among them,
+ * purges = how often the reference's map would have forgotten its little-used words (:115-144; replayed on the device,
+ * one epoch per purge), fell_back = 1 when more than CRGPU_OPT_DICPICK_EPOCHS purges made the call copy the stream to
+ * the host and run dicpick() there (same bytes; tokens / distinct then describe the device's scan, purges the cap),
+ * kernel_ms = from the first kernel to the last on the stream. Device memory: 30 bytes per token + 8 per 8 192 bytes
+ * of the stream, held by the context. crgpu_dicpick: the same from HOST memory (one copy to the device first). */
+typedef struct { uint32_t tokens, distinct, purges, fell_back; float kernel_ms; } crgpu_dicpick_info;
+int crgpu_dicpick_dev(crgpu_ctx* ctx, const uint8_t* dev_src, uint64_t n, data_block_t* dic_block, crgpu_dicpick_info* info);
+int crgpu_dicpick(crgpu_ctx* ctx, const uint8_t* host_src, uint64_t n, data_block_t* dic_block, crgpu_dicpick_info* info);
 
 /* `-F` pre-filters with the reference's signature (src/cr-filter.h:35-38; called per datablock by the
  * block loop, src/main.c:183-185 before dictionary_encode and :284-286 after dictionary_decode).
