@@ -43,6 +43,12 @@ class DicpickInfo(ctypes.Structure):
                 ("fell_back", ctypes.c_uint32), ("kernel_ms", ctypes.c_float)]
 
 
+class FilterInfo(ctypes.Structure):
+    """crgpu_filter_info."""
+    _fields_ = [("images", ctypes.c_uint32), ("pieces", ctypes.c_uint32), ("rescans", ctypes.c_uint32),
+                ("fell_back", ctypes.c_uint32), ("kernel_ms", ctypes.c_float)]
+
+
 def library_path() -> str:
     """libcrgpu.so next to this file; $CRGPU_LIB selects another build of the same ABI (e.g. the
     -DCRGPU_PROF diagnostic build used by tools/phase_profile.py)."""
@@ -107,6 +113,10 @@ def load_library():
     L.crgpu_dicpick_dev.argtypes = [vp, vp, ctypes.c_uint64, ctypes.POINTER(DataBlock), ctypes.POINTER(DicpickInfo)]
     L.crgpu_dicpick.restype = i32
     L.crgpu_dicpick.argtypes = [vp, vp, ctypes.c_uint64, ctypes.POINTER(DataBlock), ctypes.POINTER(DicpickInfo)]
+    L.crgpu_filter_blocks_dev.restype = i32
+    L.crgpu_filter_blocks_dev.argtypes = [vp, vp, vp, vp, u32, i32, vp, ctypes.POINTER(FilterInfo)]
+    L.crgpu_filter_blocks.restype = i32
+    L.crgpu_filter_blocks.argtypes = [vp, vp, vp, vp, u32, i32, vp, ctypes.POINTER(FilterInfo)]
     L.data_block_destroy.restype = None
     L.data_block_destroy.argtypes = [ctypes.POINTER(DataBlock)]
     L.crgpu_selftest.restype = i32
@@ -330,6 +340,26 @@ class CrGpu:
         """crgpu_dicpick: the same for host bytes."""
         src = np.frombuffer(bytes(data) or b"\0", dtype=np.uint8)
         return self._dicpick(self.lib.crgpu_dicpick, "crgpu_dicpick", _ptr(src), len(data))
+
+    def _filter(self, fn, what, data, off, lens, en_de):
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        touched = np.zeros(max(1, len(off)), dtype=np.uint8)
+        info = FilterInfo()
+        self._check(fn(self.h, data, _ptr(off), _ptr(lens), len(off), int(en_de), _ptr(touched), ctypes.byref(info)), what)
+        return [int(t) for t in touched[:len(off)]], {"images": info.images, "pieces": info.pieces, "rescans": info.rescans,
+                                                       "fell_back": info.fell_back, "kernel_ms": info.kernel_ms}
+
+    def filter_blocks_dev(self, d_ptr: int, off, lens, en_de: int):
+        """crgpu_filter_blocks_dev: filter_inplace over the blocks [off[b], off[b] + lens[b]) of the stream at device
+        pointer d_ptr, in place -> (touched per block, info dict)."""
+        return self._filter(self.lib.crgpu_filter_blocks_dev, "crgpu_filter_blocks_dev", ctypes.c_void_p(d_ptr), off, lens, en_de)
+
+    def filter_blocks(self, data, off, lens, en_de: int):
+        """crgpu_filter_blocks: the same for host bytes -> (filtered bytes, touched per block, info dict)."""
+        buf = np.frombuffer(bytes(data) or b"\0", dtype=np.uint8).copy()
+        touched, info = self._filter(self.lib.crgpu_filter_blocks, "crgpu_filter_blocks", _ptr(buf), off, lens, en_de)
+        return buf[:len(data)].tobytes(), touched, info
 
     def selftest(self, values, limit, index):
         inp = np.zeros(66, dtype=np.uint32)

@@ -29,6 +29,7 @@
 #include "crgpu_rolz3.h"
 #include "crgpu_rox3.h"
 #include "crgpu_dicpick.h"
+#include "crgpu_filter.h"
 
 /* ------------------------------------------------------------------ kernels */
 
@@ -950,6 +951,10 @@ struct crgpu_ctx {
     uint8_t*    d_side; size_t d_side_cap;      /* comprox chain encoder: per-block side-stream staging */
     uint8_t*    d_dic_tiles; size_t d_dic_tiles_cap;   /* crgpu_dicpick_dev: state words + per-tile token counts */
     uint8_t*    d_dic; size_t d_dic_cap;               /* crgpu_dicpick_dev: tokens, slot ids, table, hits */
+    uint8_t*    d_flt_meta; size_t d_flt_meta_cap;     /* crgpu_filter_blocks_dev: block table, counts per wave span, state words */
+    uint8_t*    d_flt_recs; size_t d_flt_recs_cap;     /* ... the scan's records */
+    uint8_t*    d_flt_snap; size_t d_flt_snap_cap;     /* ... snapshot of the blocks' span: one byte per stream byte */
+    uint8_t*    d_flt_work; size_t d_flt_work_cap;     /* ... work items, tile maps, band sums */
     uint32_t    dic_epochs;                     /* CRGPU_OPT_DICPICK_EPOCHS: purges replayed on the device before the host census takes over */
     int         one_wave_encoder;   /* CRGPU_OPT_ONE_WAVE_ENCODER: the model-carrying one-wave coders instead of the kernel pipeline */
     int         one_wave_decoder;   /* CRGPU_OPT_ONE_WAVE_DECODER: the model-carrying C++ decoders instead of the assembly step */
@@ -1162,7 +1167,7 @@ extern "C" void crgpu_destroy(crgpu_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    for (int i = 0; i < 3; i++) (void)hipFree(c->arenas[i].p); (void)hipFree(c->ticket); (void)hipFree(c->d_in); (void)hipFree(c->d_out); (void)hipFree(c->d_meta); (void)hipFree(c->d_lens); (void)hipFree(c->d_done); (void)hipFree(c->d_rox); (void)hipFree(c->d_ev); (void)hipFree(c->d_side); (void)hipFree(c->d_dic_tiles); (void)hipFree(c->d_dic); (void)hipEventDestroy(c->ev_mid); for (int i = 0; i <= CRGPU_MAX_STAGES; i++) if (c->ev_own[i]) (void)hipEventDestroy(c->ev_own[i]);
+    for (int i = 0; i < 3; i++) (void)hipFree(c->arenas[i].p); (void)hipFree(c->ticket); (void)hipFree(c->d_in); (void)hipFree(c->d_out); (void)hipFree(c->d_meta); (void)hipFree(c->d_lens); (void)hipFree(c->d_done); (void)hipFree(c->d_rox); (void)hipFree(c->d_ev); (void)hipFree(c->d_side); (void)hipFree(c->d_dic_tiles); (void)hipFree(c->d_dic); (void)hipFree(c->d_flt_meta); (void)hipFree(c->d_flt_recs); (void)hipFree(c->d_flt_snap); (void)hipFree(c->d_flt_work); (void)hipEventDestroy(c->ev_mid); for (int i = 0; i <= CRGPU_MAX_STAGES; i++) if (c->ev_own[i]) (void)hipEventDestroy(c->ev_own[i]);
     for (int i = 0; i < c->pool_n; i++) (void)hipEventDestroy(c->pool[i]);
     free(c->pool); free(c->log);
     (void)hipEventDestroy(c->ev0); (void)hipEventDestroy(c->ev1);
@@ -2082,6 +2087,222 @@ extern "C" int crgpu_dicpick(crgpu_ctx* c, const uint8_t* host_src, uint64_t n, 
         CR_TRY(c, hipMemcpyAsync(c->d_in, host_src, (size_t)n, hipMemcpyHostToDevice, c->stream));
     }
     return crgpu_dicpick_dev(c, c->d_in, n, dic_block, info);
+}
+
+/* ------------------------------------------------------------------ -F pre-filters on the device (crgpu_filter.h) */
+
+static int flt_check(crgpu_ctx* c, const void* data, const uint64_t* off, const uint32_t* len, uint32_t nb, const uint8_t* touched) {
+    if (!data || !off || !len || !touched) return CRGPU_E_ARG;
+    for (uint32_t b = 0; b < nb; b++) {
+        if (len[b] > CRGPU_MAX_BLOCK) { snprintf(c->err, sizeof c->err, "block %u: %u bytes exceed CRGPU_MAX_BLOCK", b, len[b]); return CRGPU_E_ARG; }
+        if (b && off[b] < off[b - 1] + len[b - 1]) { snprintf(c->err, sizeof c->err, "block %u overlaps its predecessor", b); return CRGPU_E_ARG; }
+    }
+    return CRGPU_OK;
+}
+
+/* end of the run of adjacent blocks that starts with block b; *bytes = its length */
+static uint32_t flt_run_end(const uint64_t* off, const uint32_t* len, uint32_t nb, uint32_t b, u64* bytes) {
+    uint32_t e = b;
+    *bytes = 0;
+    do { *bytes += len[e]; e++; } while (e < nb && off[e] == off[e - 1] + len[e - 1]);
+    return e;
+}
+
+/* copies every run of adjacent blocks. A buffer is either the stream (block b at off[b]) or `packed`: the blocks back to
+ * back, block b at the sum of the lengths in front of it - what the snapshot and the host twin's staging hold, so that
+ * neither grows with the gaps between the blocks */
+static int flt_copy_runs(crgpu_ctx* c, uint8_t* dst, int dst_packed, const uint8_t* src, int src_packed, const uint64_t* off, const uint32_t* len,
+                         uint32_t nb, hipMemcpyKind kind) {
+    u64 packed = 0;
+    for (uint32_t b = 0; b < nb;) {
+        u64 bytes;
+        const uint32_t e = flt_run_end(off, len, nb, b, &bytes);
+        if (bytes) CR_TRY(c, hipMemcpyAsync(dst + (dst_packed ? packed : off[b]), src + (src_packed ? packed : off[b]), (size_t)bytes, kind, c->stream));
+        packed += bytes;
+        b = e;
+    }
+    return CRGPU_OK;
+}
+
+/* kernel time of the group of kernels that just ended (its stream has been waited for) */
+static int flt_group_ms(crgpu_ctx* c, float* ms) {
+    float t = 0.f;
+    CR_TRY(c, hipEventElapsedTime(&t, c->ev_stage[0], c->ev_stage[c->n_stages]));
+    *ms += t;
+    return CRGPU_OK;
+}
+
+/* the host pass over blocks that lie on the device: every run of adjacent blocks to the host, filter_inplace block by
+ * block, and back */
+static int flt_host_pass(crgpu_ctx* c, uint8_t* dev, const uint64_t* off, const uint32_t* len, uint32_t nb, int en_de, uint8_t* touched) {
+    for (uint32_t b = 0; b < nb;) {
+        u64 bytes;
+        const uint32_t e = flt_run_end(off, len, nb, b, &bytes);
+        uint8_t* h = (uint8_t*)malloc(bytes ? (size_t)bytes : 1u);
+        if (!h) { snprintf(c->err, sizeof c->err, "malloc(%llu) failed", bytes); return CRGPU_E_NOMEM; }
+        hipError_t er = bytes ? hipMemcpyAsync(h, dev + off[b], (size_t)bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+        if (er == hipSuccess) er = hipStreamSynchronize(c->stream);
+        if (er == hipSuccess) {
+            u64 at = 0;
+            for (uint32_t k = b; k < e; k++) { touched[k] = (uint8_t)filter_inplace(h + at, len[k], en_de); at += len[k]; }
+            if (bytes) er = hipMemcpyAsync(dev + off[b], h, (size_t)bytes, hipMemcpyHostToDevice, c->stream);
+            if (er == hipSuccess) er = hipStreamSynchronize(c->stream);
+        }
+        free(h);
+        if (er != hipSuccess) return fail(c, er, "hipMemcpyAsync(filter host pass)");
+        b = e;
+    }
+    return CRGPU_OK;
+}
+
+/* scan (count, offsets, fill) -> *recs (malloc'ed, *nrec records in stream order) */
+static int flt_scan(crgpu_ctx* c, const uint8_t* dev_data, const uint64_t* off, const uint32_t* len, uint32_t nb, crf_rec** recs, uint32_t* nrec, uint32_t** st_out, float* ms) {
+    uint32_t* tile0 = (uint32_t*)malloc(sizeof(uint32_t) * ((size_t)nb + 1u));
+    if (!tile0) { snprintf(c->err, sizeof c->err, "malloc(tile table) failed"); return CRGPU_E_NOMEM; }
+    u64 ntiles = 0;
+    for (uint32_t b = 0; b < nb; b++) { tile0[b] = (uint32_t)ntiles; ntiles += (len[b] + CR_FLT_TILE - 1u) / CR_FLT_TILE; }
+    tile0[nb] = (uint32_t)ntiles;
+    if (ntiles == 0 || ntiles > 0x3fffffffull) { free(tile0); if (ntiles) { snprintf(c->err, sizeof c->err, "too many tiles in one call"); return CRGPU_E_ARG; } return CRGPU_OK; }
+    const u64 o_len = 8ull * nb, o_tile0 = align_up(o_len + 4ull * nb, 8), o_cnt = align_up(o_tile0 + 4ull * (nb + 1ull), 8);
+    const u64 o_st = o_cnt + 4ull * (CRF_THREADS / 64u) * ntiles;
+    int rc = grow(c, &c->d_flt_meta, &c->d_flt_meta_cap, (size_t)(o_st + 256u));
+    CrFlt F;
+    memset(&F, 0, sizeof F);
+    hipError_t e = hipSuccess;
+    if (rc == CRGPU_OK) {
+        F.src = dev_data; F.nb = nb;
+        F.off = (const u64*)c->d_flt_meta; F.len = (const uint32_t*)(c->d_flt_meta + o_len); F.tile0 = (const uint32_t*)(c->d_flt_meta + o_tile0);
+        F.cnt = (uint32_t*)(c->d_flt_meta + o_cnt); F.st = (uint32_t*)(c->d_flt_meta + o_st);
+        e = hipMemcpyAsync((void*)F.off, off, 8u * (size_t)nb, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync((void*)F.len, len, 4u * (size_t)nb, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync((void*)F.tile0, tile0, 4u * ((size_t)nb + 1u), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    }
+    free(tile0);
+    if (rc != CRGPU_OK) return rc;
+    if (e != hipSuccess) return fail(c, e, "hipMemcpyAsync(block table)");
+    *st_out = F.st;
+    uint32_t st[2] = {0, 0};
+    CR_DIC_RC(dic_group_open(c));
+    CR_DIC_STAGE("k_flt_scan_count", k_flt_scan<false>, (uint32_t)ntiles, CRF_THREADS, F);
+    CR_DIC_STAGE("k_flt_offsets", k_flt_offsets, 1, CR_DIC_BLK, F.cnt, (uint32_t)ntiles * (CRF_THREADS / 64u), F.st);
+    CR_DIC_RC(dic_group_close(c));
+    CR_TRY(c, hipMemcpyAsync(st, F.st, sizeof st, hipMemcpyDeviceToHost, c->stream));
+    CR_TRY(c, hipStreamSynchronize(c->stream));
+    CR_DIC_RC(flt_group_ms(c, ms));
+    if (!st[0]) return CRGPU_OK;
+    CR_DIC_RC(grow(c, &c->d_flt_recs, &c->d_flt_recs_cap, sizeof(crf_rec) * (size_t)st[0]));
+    F.recs = (crf_rec*)c->d_flt_recs;
+    CR_DIC_RC(dic_group_open(c));
+    CR_DIC_STAGE("k_flt_scan_fill", k_flt_scan<true>, (uint32_t)ntiles, CRF_THREADS, F);
+    CR_DIC_RC(dic_group_close(c));
+    *recs = (crf_rec*)malloc(sizeof(crf_rec) * (size_t)st[0]);
+    if (!*recs) { snprintf(c->err, sizeof c->err, "malloc(%u records) failed", st[0]); return CRGPU_E_NOMEM; }
+    CR_TRY(c, hipMemcpyAsync(*recs, F.recs, sizeof(crf_rec) * (size_t)st[0], hipMemcpyDeviceToHost, c->stream));
+    CR_TRY(c, hipStreamSynchronize(c->stream));
+    CR_DIC_RC(flt_group_ms(c, ms));
+    *nrec = st[0];
+    return CRGPU_OK;
+}
+
+/* snapshot, work items to the device, the transform kernels; *flag = the overhang flag */
+static int flt_transform(crgpu_ctx* c, uint8_t* dev_data, const uint64_t* off, const uint32_t* len, uint32_t nb, int en_de, const crf_plan* P,
+                         uint32_t* st, uint32_t* flag, float* ms) {
+    u64 bytes = 0;
+    for (uint32_t b = 0; b < nb; b++) bytes += len[b];
+    CR_DIC_RC(grow(c, &c->d_flt_snap, &c->d_flt_snap_cap, (size_t)bytes));
+    CR_DIC_RC(flt_copy_runs(c, c->d_flt_snap, 1, dev_data, 0, off, len, nb, hipMemcpyDeviceToDevice));
+    const u64 o_bmp = align_up(sizeof(crf_e8) * (u64)P->n_e8, 8), o_tmap = align_up(o_bmp + sizeof(crf_bmp) * (u64)P->n_bmp, 8);
+    const u64 o_sums = o_tmap + 4ull * P->e8_wgs, total = o_sums + 4ull * P->sums;
+    CR_DIC_RC(grow(c, &c->d_flt_work, &c->d_flt_work_cap, (size_t)total + 8u));
+    if (P->n_e8) CR_TRY(c, hipMemcpyAsync(c->d_flt_work, P->e8, sizeof(crf_e8) * (size_t)P->n_e8, hipMemcpyHostToDevice, c->stream));
+    if (P->n_bmp) CR_TRY(c, hipMemcpyAsync(c->d_flt_work + o_bmp, P->bmp, sizeof(crf_bmp) * (size_t)P->n_bmp, hipMemcpyHostToDevice, c->stream));
+    CrFltE8 E;
+    E.snap = c->d_flt_snap; E.dst = dev_data; E.items = (const crf_e8*)c->d_flt_work; E.n = P->n_e8;
+    E.tmap = (uint32_t*)(c->d_flt_work + o_tmap); E.st = st; E.decode = en_de != 0;
+    CrFltBmp B;
+    B.snap = c->d_flt_snap; B.dst = dev_data; B.items = (const crf_bmp*)(c->d_flt_work + o_bmp); B.n = P->n_bmp;
+    B.sums = (uint32_t*)(c->d_flt_work + o_sums);
+    CR_DIC_RC(dic_group_open(c));
+    if (P->n_e8) {
+        CR_DIC_STAGE("k_flt_e8_map", k_flt_e8_map, P->e8_wgs, CRF_THREADS, E);
+        CR_DIC_STAGE("k_flt_e8e9", k_flt_e8e9, P->e8_wgs, CRF_THREADS, E);
+    }
+    if (P->n_bmp && !en_de) CR_DIC_STAGE("k_flt_bmp_enc", k_flt_bmp_enc, P->wg_px, CRF_THREADS, B);
+    if (P->n_bmp && en_de) {
+        CR_DIC_STAGE("k_flt_bmp_rows", k_flt_bmp_rows, P->wg_row, CRF_THREADS, B);
+        CR_DIC_STAGE("k_flt_bmp_colsum", k_flt_bmp_colsum, P->wg_band, CRF_THREADS, B);
+        CR_DIC_STAGE("k_flt_bmp_cols", k_flt_bmp_cols, P->wg_band, CRF_THREADS, B);
+    }
+    if (P->n_watch) CR_DIC_STAGE("k_flt_watch", k_flt_watch, (P->n_e8 + CRF_THREADS / 64u - 1u) / (CRF_THREADS / 64u), CRF_THREADS, E);
+    CR_DIC_RC(dic_group_close(c));
+    if (P->n_watch) CR_TRY(c, hipMemcpyAsync(flag, st + 1, sizeof *flag, hipMemcpyDeviceToHost, c->stream));
+    CR_TRY(c, hipStreamSynchronize(c->stream));                         /* the work items are the caller's to free */
+    return flt_group_ms(c, ms);
+}
+
+extern "C" int crgpu_filter_blocks_dev(crgpu_ctx* c, uint8_t* dev_data, const uint64_t* off, const uint32_t* len, uint32_t nb, int en_de,
+                                       uint8_t* touched, crgpu_filter_info* info) {
+    if (!c) return CRGPU_E_ARG;
+    crgpu_filter_info I;
+    memset(&I, 0, sizeof I);
+    if (info) *info = I;
+    if (nb == 0) return CRGPU_OK;
+    CR_DIC_RC(flt_check(c, dev_data, off, len, nb, touched));
+    CR_TRY(c, hipSetDevice(c->device));
+    memset(touched, 0, nb);
+    CR_TRY(c, hipEventRecord(c->ev0, c->stream));
+    CR_TRY(c, hipEventRecord(c->ev_mid, c->stream));
+    crf_rec* recs = NULL;
+    uint32_t nrec = 0, flag = 0;
+    uint32_t* st = NULL;
+    int rc = flt_scan(c, dev_data, off, len, nb, &recs, &nrec, &st, &I.kernel_ms);
+    crf_saved entry;
+    crf_plan P;
+    memset(&P, 0, sizeof P);
+    crf_state_save(&entry);
+    if (rc == CRGPU_OK) {
+        rc = crf_plan_blocks(recs, nrec, off, len, nb, en_de, touched, &P);
+        if (rc != CRGPU_OK) snprintf(c->err, sizeof c->err, "malloc(work items) failed");
+    }
+    if (rc == CRGPU_OK && (P.n_e8 || P.n_bmp)) rc = flt_transform(c, dev_data, off, len, nb, en_de, &P, st, &flag, &I.kernel_ms);
+    I.images = nrec; I.pieces = P.n_e8 + P.n_bmp;
+    if (rc != CRGPU_OK) (void)hipStreamSynchronize(c->stream);          /* copies from the work items may still be queued */
+    crf_plan_free(&P);
+    free(recs);
+    if (rc == CRGPU_OK && flag) {
+        /* a signature in the bytes an ELF pass rewrote behind its claim: the records may not be what the host pass would
+         * have seen. The original bytes come back from the snapshot, the state from the call's entry, and the host runs. */
+        I.fell_back = 1;
+        crf_state_restore(&entry);
+        rc = flt_copy_runs(c, dev_data, 0, c->d_flt_snap, 1, off, len, nb, hipMemcpyDeviceToDevice);
+        if (rc == CRGPU_OK) rc = flt_host_pass(c, dev_data, off, len, nb, en_de, touched);
+    }
+    if (rc != CRGPU_OK) { crf_state_restore(&entry); return rc; }
+    CR_TRY(c, hipEventRecord(c->ev1, c->stream));
+    c->timed = 1;
+    if (info) *info = I;
+    return CRGPU_OK;
+}
+
+extern "C" int crgpu_filter_blocks(crgpu_ctx* c, uint8_t* host_data, const uint64_t* off, const uint32_t* len, uint32_t nb, int en_de,
+                                   uint8_t* touched, crgpu_filter_info* info) {
+    if (!c) return CRGPU_E_ARG;
+    if (nb == 0) return crgpu_filter_blocks_dev(c, NULL, off, len, 0, en_de, touched, info);
+    CR_DIC_RC(flt_check(c, host_data, off, len, nb, touched));
+    CR_TRY(c, hipSetDevice(c->device));
+    uint64_t* rel = (uint64_t*)malloc(sizeof(uint64_t) * (size_t)nb);
+    if (!rel) { snprintf(c->err, sizeof c->err, "malloc(offsets) failed"); return CRGPU_E_NOMEM; }
+    u64 bytes = 0;                                                      /* on the device the blocks lie back to back */
+    for (uint32_t b = 0; b < nb; b++) { rel[b] = bytes; bytes += len[b]; }
+    int rc = grow(c, &c->d_in, &c->d_in_cap, (size_t)bytes + 1u);
+    if (rc == CRGPU_OK) rc = flt_copy_runs(c, c->d_in, 1, host_data, 0, off, len, nb, hipMemcpyHostToDevice);
+    if (rc == CRGPU_OK) rc = crgpu_filter_blocks_dev(c, c->d_in, rel, len, nb, en_de, touched, info);
+    if (rc == CRGPU_OK) rc = flt_copy_runs(c, host_data, 0, c->d_in, 1, off, len, nb, hipMemcpyDeviceToHost);
+    free(rel);
+    if (rc != CRGPU_OK) return rc;
+    CR_TRY(c, hipStreamSynchronize(c->stream));
+    return CRGPU_OK;
 }
 
 /* wave-primitive self test: in = 66 u32 (64 lane values, mask limit, table index), out = 384 u32 */

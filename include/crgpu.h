@@ -360,6 +360,26 @@ int  crgpu_filter_mode(void);
  * from FILTER_DEC — neither here nor in the reference. comp*-gpu -F prints a warning when it happens (also under -q). */
 int  crgpu_filter_lossy(void);
 
+/* filter_inplace for blocks that lie in device memory (csrc/crgpu_filter.h): after the call dev_data holds exactly the
+ * bytes that filter_inplace(data + off[b], len[b], en_de) leaves when called for b = 0..nb-1 in order, touched[b] (host
+ * memory, nb entries) is that call's return value, and the process-wide filter state (the open image, the mode, the
+ * lossy count) is what those calls leave: a stream may be fed in slices, host and device calls may be mixed,
+ * crgpu_filter_reset() clears it for both. off is ascending, the blocks do not overlap, len[b] <= CRGPU_MAX_BLOCK
+ * (CRGPU_E_ARG otherwise); nothing outside the blocks is read or written. The device finds and analyses the image
+ * headers, the host walks the filters' state machines over what it found (a few decisions per image), the device
+ * transforms — from a snapshot of the blocks (packed back to back: gaps between the blocks cost nothing), so the
+ * context holds one byte of device memory per byte of the blocks plus 32 bytes per header found. The call returns when the stream is done. info (may be NULL): images = headers
+ * that passed a filter's analysis, pieces = ranges transformed, fell_back = 1 when an ELF image's pass rewrote bytes
+ * behind its claimed length that hold a header signature (before or after): the call then restored the stream and ran
+ * filter_inplace on the host (same bytes); rescans is reserved (0); kernel_ms = the kernels' time (HIP events around each group
+ * of kernels, summed; readbacks, the plan and the copies are not in it).
+ * crgpu_filter_blocks: the same for HOST memory, one copy in and one out per run of adjacent blocks (staged back to back). */
+typedef struct { uint32_t images, pieces, rescans, fell_back; float kernel_ms; } crgpu_filter_info;
+int crgpu_filter_blocks_dev(crgpu_ctx* ctx, uint8_t* dev_data, const uint64_t* off, const uint32_t* len, uint32_t nb,
+                            int en_de, uint8_t* touched, crgpu_filter_info* info);
+int crgpu_filter_blocks(crgpu_ctx* ctx, uint8_t* host_data, const uint64_t* off, const uint32_t* len, uint32_t nb,
+                        int en_de, uint8_t* touched, crgpu_filter_info* info);
+
 #ifdef __cplusplus
 }
 #endif
