@@ -95,6 +95,18 @@ def load_library():
     L.crgpu_encode_blocks.argtypes = [vp, i32, vp, vp, vp, u32, vp, vp, vp]
     L.crgpu_decode_blocks.restype = i32
     L.crgpu_decode_blocks.argtypes = [vp, i32, vp, vp, vp, u32, vp, vp, vp, vp]
+    L.crgpu_models_create.restype = i32
+    L.crgpu_models_create.argtypes = [vp, ctypes.POINTER(vp)]
+    L.crgpu_models_destroy.restype = None
+    L.crgpu_models_destroy.argtypes = [vp]
+    L.crgpu_models_reset.restype = i32
+    L.crgpu_models_reset.argtypes = [vp, vp]
+    L.crgpu_encode_blocks_carried_dev.restype = i32
+    L.crgpu_encode_blocks_carried_dev.argtypes = [vp, i32, vp, vp, vp, vp, u32, vp, vp, vp]
+    L.crgpu_encode_blocks_carried.restype = i32
+    L.crgpu_encode_blocks_carried.argtypes = [vp, i32, vp, vp, vp, vp, u32, vp, vp, vp]
+    L.crgpu_shim_pipeline_carry.restype = None
+    L.crgpu_shim_pipeline_carry.argtypes = [i32]
     L.crgpu_dict_create.restype = i32
     L.crgpu_dict_create.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp)]
     L.crgpu_dict_destroy.restype = None
@@ -258,8 +270,9 @@ class CrGpu:
         return {names[i].decode(): (float(ms[i]), int(cnt[i])) for i in range(n)}
 
     # ---- host-pointer batch API -------------------------------------------------
-    def encode_blocks(self, blocks, codec: int = CODEC_ROP):
-        """blocks: list of bytes-like. Returns list of encoded bytes (independent datablocks)."""
+    def encode_blocks(self, blocks, codec: int = CODEC_ROP, models: "CrModels" = None):
+        """blocks: list of bytes-like. Returns list of encoded bytes: independent datablocks, or with `models` (comprop)
+        a run of dependent ones — block 0 continues the models' state, block i block i - 1, the models keep what the last leaves."""
         nb = len(blocks)
         if nb == 0:
             return []
@@ -272,8 +285,12 @@ class CrGpu:
         out_off[1:] = np.cumsum(caps[:-1], dtype=np.uint64)
         out = np.zeros(int(caps.sum()), dtype=np.uint8)
         out_size = np.zeros(nb, dtype=np.uint32)
-        self._check(self.lib.crgpu_encode_blocks(self.h, codec, _ptr(src), _ptr(in_off), _ptr(sizes), nb,
-                                                 _ptr(out), _ptr(out_off), _ptr(out_size)), "crgpu_encode_blocks")
+        if models is not None:
+            self._check(self.lib.crgpu_encode_blocks_carried(self.h, codec, models.h, _ptr(src), _ptr(in_off), _ptr(sizes), nb,
+                                                             _ptr(out), _ptr(out_off), _ptr(out_size)), "crgpu_encode_blocks_carried")
+        else:
+            self._check(self.lib.crgpu_encode_blocks(self.h, codec, _ptr(src), _ptr(in_off), _ptr(sizes), nb,
+                                                     _ptr(out), _ptr(out_off), _ptr(out_size)), "crgpu_encode_blocks")
         return [out[int(o):int(o) + int(s)].tobytes() for o, s in zip(out_off, out_size)]
 
     def decode_blocks(self, blocks, caps, codec: int = CODEC_ROP, strict: bool = True):
@@ -304,6 +321,15 @@ class CrGpu:
         self._check(self.lib.crgpu_encode_blocks_dev(self.h, codec, d_in, d_in_off, d_in_size, nblocks, max_block,
                                                      d_out, d_out_off, d_out_size, int(sync)),
                     "crgpu_encode_blocks_dev")
+
+    def encode_blocks_carried_dev(self, models, d_in, d_in_off, d_in_size, nblocks, d_out, d_out_off, d_out_size,
+                                  codec=CODEC_ROP):
+        """Dependent comprop blocks on the kernel pipeline, everything in device memory; returns when they are coded."""
+        self._check(self.lib.crgpu_encode_blocks_carried_dev(self.h, codec, models.h, d_in, d_in_off, d_in_size, nblocks,
+                                                             d_out, d_out_off, d_out_size), "crgpu_encode_blocks_carried_dev")
+
+    def models_create(self) -> "CrModels":
+        return CrModels(self)
 
     def decode_blocks_dev(self, codec, d_in, d_in_off, d_in_size, nblocks, max_block, d_out, d_out_off, d_out_cap,
                           d_out_size, sync=False):
@@ -475,6 +501,29 @@ class CrMulti:
 
     def decode_blocks(self, blocks, codec: int = CODEC_ROP, flags: int = 0, prec=None):
         return self._run(self.lib.crgpu_multi_decode_blocks, "crgpu_multi_decode_blocks", codec, flags, blocks, prec)
+
+
+class CrModels:
+    """comprop's PPM models in device memory (crgpu_models): they outlive the call, as the reference's do until reset_models()."""
+
+    def __init__(self, gpu: CrGpu):
+        self.gpu = gpu
+        self.h = ctypes.c_void_p()
+        gpu._check(gpu.lib.crgpu_models_create(gpu.h, ctypes.byref(self.h)), "crgpu_models_create")
+
+    def reset(self):
+        self.gpu._check(self.gpu.lib.crgpu_models_reset(self.gpu.h, self.h), "crgpu_models_reset")
+
+    def close(self):
+        if self.h:
+            self.gpu.lib.crgpu_models_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class CrDict:

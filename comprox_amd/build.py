@@ -16,9 +16,11 @@ CLI = os.path.join(HERE, "bin", "comprop-gpu")
 CLI_ROX = os.path.join(HERE, "bin", "comprox-gpu")
 CLI_ROLZ = os.path.join(HERE, "bin", "comprolz-gpu")
 EXTRA_LIBS = ["-lpthread", "-ldl"]
-SOURCES = ["crgpu.hip", "crgpu_multi.hip"]            # HIP: kernels + C-ABI; the multi-GPU block loop
+# per-source compile flags: the carried-model kernels are built without the packed fp32 forms (they are integer code in any case)
+SOURCE_FLAGS = {"crgpu_carry.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+SOURCES = ["crgpu.hip", "crgpu_carry.hip", "crgpu_multi.hip"]   # HIP: kernels + C-ABI; the carried-model kernels; the multi-GPU block loop
 HOST_C = ["crhost_dict.c", "crhost_filter.c"]         # plain C host passes (gcc), linked into the same library
-HEADERS = ["crgpu_device.h", "crgpu_wave.h", "crgpu_ppm.h", "crgpu_lzp.h", "crgpu_lzp2.h", "crgpu_links2.h", "crgpu_rolz3.h", "crgpu_rox3.h", "crgpu_rop.h", "crgpu_dict.h", "crgpu_rox.h", "crgpu_rolz.h", "crgpu_rop2.h", "crgpu_dec.h", "crgpu_rop5.h", "crgpu_rox5.h", "crgpu_rolz5.h", "crgpu_rox2.h", "crgpu_rolz2.h", "crgpu_dicpick.h", "crgpu_filter.h"]
+HEADERS = ["crgpu_device.h", "crgpu_wave.h", "crgpu_ppm.h", "crgpu_lzp.h", "crgpu_lzp2.h", "crgpu_links2.h", "crgpu_carry.h", "crgpu_rolz3.h", "crgpu_rox3.h", "crgpu_rop.h", "crgpu_dict.h", "crgpu_rox.h", "crgpu_rolz.h", "crgpu_rop2.h", "crgpu_dec.h", "crgpu_rop5.h", "crgpu_rox5.h", "crgpu_rolz5.h", "crgpu_rox2.h", "crgpu_rolz2.h", "crgpu_dicpick.h", "crgpu_filter.h"]
 
 
 def _stale() -> bool:
@@ -47,7 +49,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         objs.append(obj)
     for src in SOURCES:
         obj = os.path.join(CSRC, os.path.splitext(src)[0] + ".o")
-        cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-c", os.path.join(CSRC, src), "-o", obj]
+        cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17"] + SOURCE_FLAGS.get(src, []) + ["-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
             cmd.append("-Rpass-analysis=kernel-resource-usage")
             print(" ".join(cmd), file=sys.stderr)
@@ -71,7 +73,7 @@ def _build_diag(flags, verbose: bool = False) -> str:
         objs.append(obj)
     for src in SOURCES:
         obj = os.path.join(CSRC, os.path.splitext(src)[0] + ".diag.o")
-        cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17"] + flags + ["-c", os.path.join(CSRC, src), "-o", obj]
+        cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17"] + SOURCE_FLAGS.get(src, []) + flags + ["-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         subprocess.run(cmd, check=True)

@@ -26,6 +26,7 @@
 #include "crgpu_rolz2.h"
 #include "crgpu_lzp2.h"
 #include "crgpu_links2.h"
+#include "crgpu_carry.h"
 #include "crgpu_rolz3.h"
 #include "crgpu_rox3.h"
 #include "crgpu_dicpick.h"
@@ -1322,7 +1323,123 @@ static uint32_t cr_resident_grid(crgpu_ctx* c, const void* kernel, uint32_t thre
 }
 #define CR_G(kernel_, threads_, dyn_) dim3(cr_resident_grid(c, reinterpret_cast<const void*>(kernel_), (threads_), (dyn_), grid))
 
-static int launch(crgpu_ctx* c, int codec, int decode, CrBatch& B, uint32_t max_block, int sync) {
+/* ------------------------------------------------------------------ carried models (crgpu_carry.h) */
+
+struct crgpu_models {
+    crgpu_ctx* ctx;
+    uint8_t*   d;        /* the store, CR_M_BYTES */
+    uint8_t*   d_keep;   /* its copy from in front of the block being coded: the abort point goes back to it */
+};
+
+extern "C" int crgpu_models_reset(crgpu_ctx* c, crgpu_models* m) {
+    if (!c || !m || m->ctx != c) return CRGPU_E_ARG;
+    CR_TRY(c, hipSetDevice(c->device));
+    crc_launch_fill(c->stream, (uint32_t)c->num_cu * 4u, m->d);
+    CR_TRY(c, hipGetLastError());
+    return CRGPU_OK;
+}
+
+extern "C" int crgpu_models_create(crgpu_ctx* c, crgpu_models** out) {
+    if (!c || !out) return CRGPU_E_ARG;
+    *out = NULL;
+    CR_TRY(c, hipSetDevice(c->device));
+    crgpu_models* m = (crgpu_models*)calloc(1, sizeof *m);
+    if (!m) return CRGPU_E_NOMEM;
+    m->ctx = c;
+    if (hipMalloc((void**)&m->d, (size_t)CR_M_BYTES) != hipSuccess || hipMalloc((void**)&m->d_keep, (size_t)CR_M_BYTES) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(m->d); free(m);
+        snprintf(c->err, sizeof c->err, "hipMalloc(model store, 2 x %llu bytes) failed", (unsigned long long)CR_M_BYTES);
+        return CRGPU_E_NOMEM;
+    }
+    const int rc = crgpu_models_reset(c, m);
+    if (rc != CRGPU_OK) { (void)hipFree(m->d); (void)hipFree(m->d_keep); free(m); return rc; }
+    *out = m;
+    return CRGPU_OK;
+}
+
+extern "C" void crgpu_models_destroy(crgpu_models* m) {
+    if (!m) return;
+    (void)hipSetDevice(m->ctx->device);
+    (void)hipStreamSynchronize(m->ctx->stream);
+    (void)hipFree(m->d); (void)hipFree(m->d_keep);
+    free(m);
+}
+
+static int carry_group_open(crgpu_ctx* c) { c->n_stages = 0; return stage_begin(c); }
+static int carry_group_close(crgpu_ctx* c) {
+    CR_TRY(c, hipEventRecord(c->ev_stage[c->n_stages], c->stream));
+    return stage_end(c);
+}
+#define CR_CARRY_STAGE(name_, ...) do { \
+        if (c->n_stages >= CRGPU_MAX_STAGES) { snprintf(c->err, sizeof c->err, "internal: more than %d kernels in one group", CRGPU_MAX_STAGES); return CRGPU_E_ARG; } \
+        CR_TRY(c, hipEventRecord(c->ev_stage[c->n_stages], c->stream)); \
+        __VA_ARGS__; \
+        CR_TRY(c, hipGetLastError()); \
+        c->stage_name[c->n_stages++] = name_; \
+    } while (0)
+#define CR_CARRY_RC(call_) do { const int rc_ = (call_); if (rc_ != CRGPU_OK) return rc_; } while (0)
+
+/* one block's events -> triples: the sorts of crgpu_rop2.h / crgpu_links2.h (in LDS where `lds` allows and the events fit), then
+ * the store-backed chain kernels. The chains of ONE block are all the parallel work there is, so the order-3 and order-2 kernels
+ * get as many workgroups as the block can have chains for (n bytes: up to 2 n events) */
+static int carried_chain_stages(crgpu_ctx* c, CrBatch B1, const CrArenaLayout& LY, uint8_t* M, uint32_t n, int lds) {
+    B1.links_lds = lds && !c->lzp_tables_only ? 1u : 0u;
+    B1.o2_tickets = c->lzp_tables_only ? 1u : 0u;
+    CR_TRY(c, hipMemsetAsync(c->ticket, 0, 128, c->stream));
+    if (B1.links_lds) {
+        if (!c->links_lds_ready) {
+            CR_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_rop_links_lds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)CR_LZ2_LDS_BYTES));
+            CR_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_rop_links_lds64), hipFuncAttributeMaxDynamicSharedMemorySize, (int)CR_LK4_LDS_BYTES));
+            c->links_lds_ready = 1;
+        }
+        CR_CARRY_STAGE("k_rop_links_lds", hipLaunchKernelGGL(k_rop_links_lds, dim3(1), dim3(CR_LZ2_THREADS), CR_LZ2_LDS_BYTES, c->stream, B1, LY));
+        if (n > CR_LZ2_MAXN / 2u) CR_CARRY_STAGE("k_rop_links_lds64", hipLaunchKernelGGL(k_rop_links_lds64, dim3(1), dim3(CR_LK4_THREADS), CR_LK4_LDS_BYTES, c->stream, B1, LY));
+    }
+    CR_CARRY_STAGE("k_rop_links", hipLaunchKernelGGL(k_rop_links, dim3(1), dim3(CR_SORT_THREADS), 0, c->stream, B1, LY));
+    const uint32_t cus = (uint32_t)c->num_cu;
+    uint32_t g3 = n / 16384u + 1u, g2 = n / 2048u + 1u;
+    if (g3 > cus * 4u) g3 = cus * 4u;
+    if (g2 > cus * 8u) g2 = cus * 8u;
+    CR_CARRY_STAGE("k_ropc_o3", crc_launch_o3(c->stream, g3, B1, M));
+    CR_CARRY_STAGE("k_ropc_o2", crc_launch_o2(c->stream, g2, B1, M));
+    CR_CARRY_STAGE("k_ropc_o1", crc_launch_o1(c->stream, B1, M));
+    return CRGPU_OK;
+}
+
+/* the blocks of a carried call, one after the other on the context's stream; B is the whole batch, its pre-pass done */
+static int carried_blocks(crgpu_ctx* c, const CrBatch& B, const CrArenaLayout& LY, crgpu_models* m, const uint32_t* h_size) {
+    for (uint32_t b = 0; b < B.nblocks; b++) {
+        const uint32_t n = h_size[b];
+        CrBatch B1 = B;
+        B1.in_off += b; B1.in_size += b; B1.out_off += b; B1.out_size += b; B1.nblocks = 1;
+        B1.ev += (u64)b * B.ev_stride; B1.lens += (u64)b * B.lens_stride; B1.pre_done += b;
+        if (B1.stats) B1.stats += (u64)b * 16u;
+        const bool models_move = n >= 16u;                       /* cr-coder.c:140-142: a block under 16 bytes touches nothing */
+        CR_CARRY_RC(carry_group_open(c));
+        if (models_move) CR_TRY(c, hipMemcpyAsync(m->d_keep, m->d, (size_t)CR_M_BYTES, hipMemcpyDeviceToDevice, c->stream));
+        CR_CARRY_STAGE("k_ropc_events", crc_launch_events(c->stream, B1, LY, m->d));
+        CR_CARRY_RC(carried_chain_stages(c, B1, LY, m->d, n, 1));
+        CR_CARRY_STAGE("k_rop_rc", hipLaunchKernelGGL(k_rop_rc, dim3(1), dim3(CRGPU_WAVE), 0, c->stream, B1, LY));
+        CR_CARRY_RC(carry_group_close(c));
+        if (!models_move) continue;
+        /* lzencode leaves its loop at the first token behind which the output is no smaller than the input and keeps the models
+         * as they stood there (cr-coder.c:204-206, 218-228); the chain kernels have walked the whole block. Rare: the store goes
+         * back to its copy and the chains run again over the events up to that token (k_ropc_abort cuts the list) */
+        uint32_t got = 0;
+        CR_TRY(c, hipMemcpyAsync(&got, B1.out_size, 4, hipMemcpyDeviceToHost, c->stream));
+        CR_TRY(c, hipStreamSynchronize(c->stream));
+        if (got != n + CRGPU_ROP_HEADER) continue;
+        CR_CARRY_RC(carry_group_open(c));
+        CR_TRY(c, hipMemcpyAsync(m->d, m->d_keep, (size_t)CR_M_BYTES, hipMemcpyDeviceToDevice, c->stream));
+        CR_CARRY_STAGE("k_ropc_abort", crc_launch_abort(c->stream, B1, m->d));
+        CR_CARRY_RC(carried_chain_stages(c, B1, LY, m->d, n, 0));
+        CR_CARRY_RC(carry_group_close(c));
+    }
+    return CRGPU_OK;
+}
+
+static int launch(crgpu_ctx* c, int codec, int decode, CrBatch& B, uint32_t max_block, int sync, crgpu_models* models = NULL, const uint32_t* h_size = NULL) {
     if (codec != CRGPU_CODEC_ROP && codec != CRGPU_CODEC_ROX && codec != CRGPU_CODEC_ROLZ) { snprintf(c->err, sizeof c->err, "codec %d not available", codec); return CRGPU_E_ARG; }
     if (max_block > CRGPU_MAX_BLOCK + 1u) { snprintf(c->err, sizeof c->err, "block of %u bytes exceeds CRGPU_MAX_BLOCK + 1", max_block); return CRGPU_E_ARG; }
     CR_TRY(c, hipSetDevice(c->device));
@@ -1533,7 +1650,15 @@ static int launch(crgpu_ctx* c, int codec, int decode, CrBatch& B, uint32_t max_
         CR_STAGE("k_rop_lzp", hipLaunchKernelGGL(k_rop_lzp, dim3(lzp_grid), dim3(256), 0, c->stream, B, LY));
         CR_TRY(c, hipGetLastError());
         CR_TRY(c, hipEventRecord(c->ev_mid, c->stream));
-        if (chains) {
+        if (chains && models) {                              /* the pre-pass was the whole batch's; the model-dependent kernels go block after block, a stage group each */
+            CR_TRY(c, hipEventRecord(c->ev_stage[c->n_stages], c->stream));
+            rc = stage_end(c);
+            if (rc == CRGPU_OK) rc = carried_blocks(c, B, LY, models, h_size);
+            if (rc != CRGPU_OK) return rc;
+            c->n_stages = 0;
+            rc = stage_begin(c);
+            if (rc != CRGPU_OK) return rc;
+        } else if (chains) {
             CR_STAGE("k_rop_events", hipLaunchKernelGGL(k_rop_events, CR_G(k_rop_events, CRGPU_WAVE, 0), dim3(CRGPU_WAVE), 0, c->stream, B, LY));
             CR_LINKS_STAGES();
             CR_STAGE("k_rop_o3", hipLaunchKernelGGL(k_rop_o3, CR_G(k_rop_o3, 256, 0), dim3(256), 0, c->stream, B, LY));
@@ -1575,6 +1700,32 @@ extern "C" int crgpu_decode_blocks_dev(crgpu_ctx* c, int codec, const uint8_t* i
     B.in = in; B.in_off = (const u64*)in_off; B.in_size = in_size;
     B.out = out; B.out_off = (const u64*)out_off; B.out_cap = out_cap; B.out_size = out_size; B.nblocks = nblocks;
     return launch(c, codec, 1, B, max_block, sync);
+}
+
+/* Block 0 starts from the models in `m`, block i continues block i - 1, `m` holds the state behind the last block; every block's
+ * bytes are what the reference's lzencode writes for it in that sequence. Returns when the blocks are coded (the abort point
+ * needs every block's size on the host). */
+extern "C" int crgpu_encode_blocks_carried_dev(crgpu_ctx* c, int codec, crgpu_models* m, const uint8_t* in, const uint64_t* in_off,
+                                               const uint32_t* in_size, uint32_t nblocks,
+                                               uint8_t* out, const uint64_t* out_off, uint32_t* out_size) {
+    if (!c || !m || m->ctx != c || (nblocks && (!in || !in_off || !in_size || !out || !out_off || !out_size))) return CRGPU_E_ARG;
+    if (codec != CRGPU_CODEC_ROP) { snprintf(c->err, sizeof c->err, "models are carried for comprop only (codec %d)", codec); return CRGPU_E_ARG; }
+    if (c->persist || c->one_wave_encoder) { snprintf(c->err, sizeof c->err, "carried models run on the kernel pipeline: not on a one-wave context"); return CRGPU_E_ARG; }
+    if (nblocks == 0) return CRGPU_OK;
+    CR_TRY(c, hipSetDevice(c->device));
+    uint32_t* h_size = (uint32_t*)malloc(sizeof(uint32_t) * nblocks);
+    if (!h_size) return CRGPU_E_NOMEM;
+    hipError_t e = hipMemcpyAsync(h_size, in_size, sizeof(uint32_t) * nblocks, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { free(h_size); return fail(c, e, "hipMemcpyAsync(block sizes)"); }
+    uint32_t max_block = 0;
+    for (uint32_t b = 0; b < nblocks; b++) if (h_size[b] > max_block) max_block = h_size[b];
+    CrBatch B; memset(&B, 0, sizeof B);
+    B.in = in; B.in_off = (const u64*)in_off; B.in_size = in_size;
+    B.out = out; B.out_off = (const u64*)out_off; B.out_size = out_size; B.nblocks = nblocks;
+    const int rc = launch(c, codec, 0, B, max_block, 1, m, h_size);
+    free(h_size);
+    return rc;
 }
 
 /* ------------------------------------------------------------------ static dictionary (device copy) */
@@ -1822,7 +1973,7 @@ static int grow(crgpu_ctx* c, uint8_t** p, size_t* cap, size_t want) {
 
 static int host_call(crgpu_ctx* c, int codec, crgpu_dict* dict, int decode, const uint8_t* in, const uint64_t* in_off,
                      const uint32_t* in_size, uint32_t nblocks, uint8_t* out, const uint64_t* out_off,
-                     const uint32_t* out_cap, uint32_t* out_size) {
+                     const uint32_t* out_cap, uint32_t* out_size, crgpu_models* models = NULL) {
     if (!c) return CRGPU_E_ARG;
     if (nblocks == 0) return CRGPU_OK;
     if (!in || !in_off || !in_size || !out || !out_off || !out_size || (decode && !out_cap)) return CRGPU_E_ARG;
@@ -1876,6 +2027,7 @@ static int host_call(crgpu_ctx* c, int codec, crgpu_dict* dict, int decode, cons
     if (dict && decode) rc = crgpu_dict_decode_blocks_dev(c, dict, c->d_in, d_in_off, d_in_size, nblocks, max_block, c->d_out, d_out_off, d_cap, d_out_size, 0);
     else if (dict)      rc = crgpu_dict_encode_blocks_dev(c, dict, c->d_in, d_in_off, d_in_size, nblocks, max_block, c->d_out, d_out_off, d_out_size, 0);
     else if (decode)    rc = crgpu_decode_blocks_dev(c, codec, c->d_in, d_in_off, d_in_size, nblocks, max_block, c->d_out, d_out_off, d_cap, d_out_size, 0);
+    else if (models)    rc = crgpu_encode_blocks_carried_dev(c, codec, models, c->d_in, d_in_off, d_in_size, nblocks, c->d_out, d_out_off, d_out_size);
     else                rc = crgpu_encode_blocks_dev(c, codec, c->d_in, d_in_off, d_in_size, nblocks, max_block, c->d_out, d_out_off, d_out_size, 0);
     if (rc == CRGPU_OK) {
         e = hipMemcpyAsync(out_size, d_out_size, 4u * nblocks, hipMemcpyDeviceToHost, c->stream);
@@ -1908,6 +2060,13 @@ extern "C" int crgpu_encode_blocks(crgpu_ctx* c, int codec, const uint8_t* in, c
                                    const uint32_t* in_size, uint32_t nblocks, uint8_t* out,
                                    const uint64_t* out_off, uint32_t* out_size) {
     return host_call(c, codec, NULL, 0, in, in_off, in_size, nblocks, out, out_off, NULL, out_size);
+}
+extern "C" int crgpu_encode_blocks_carried(crgpu_ctx* c, int codec, crgpu_models* m, const uint8_t* in, const uint64_t* in_off,
+                                           const uint32_t* in_size, uint32_t nblocks, uint8_t* out,
+                                           const uint64_t* out_off, uint32_t* out_size) {
+    if (!m) return CRGPU_E_ARG;
+    if (c && codec != CRGPU_CODEC_ROP) { snprintf(c->err, sizeof c->err, "models are carried for comprop only (codec %d)", codec); return CRGPU_E_ARG; }
+    return host_call(c, codec, NULL, 0, in, in_off, in_size, nblocks, out, out_off, NULL, out_size, m);
 }
 extern "C" int crgpu_decode_blocks(crgpu_ctx* c, int codec, const uint8_t* in, const uint64_t* in_off,
                                    const uint32_t* in_size, uint32_t nblocks, uint8_t* out,
@@ -2483,8 +2642,22 @@ static void replay_keep(int kind, const uint8_t* data, uint32_t n, uint32_t cap)
     g_replay.kind = kind; g_replay.n = n; g_replay.cap = cap;
 }
 
+/* crgpu_shim_pipeline_carry: comprop's lzencode on the kernel pipeline with ONE store of carried models for the process
+ * (crgpu_carry.h). g_carry: -1 not asked yet (the environment decides at the first shim call), 0 off, 1 on.
+ * g_carry_state: what the store holds — 0 nothing yet / to be reset before the next block, 1 the models behind the last
+ * lzencode. */
+static int g_carry = -1;
+static int g_carry_state = 0;
+static crgpu_models* g_carry_models;
+extern "C" void crgpu_shim_pipeline_carry(int on) { g_carry = on != 0; }
+static int shim_carry(int codec) {
+    if (g_carry < 0) { const char* e = getenv("CRGPU_SHIM_PIPELINE_CARRY"); g_carry = e && *e && atoi(e) != 0; }
+    return g_carry && codec == CRGPU_CODEC_ROP;
+}
+
 extern "C" void reset_models(void) {
     g_fresh = 1;
+    g_carry_state = 0;
     replay_drop();
     if (g_shim) g_shim->next_fresh = 1;        /* a context that does not exist yet starts fresh anyway */
 }
@@ -2544,12 +2717,27 @@ extern "C" void lzencode(data_block_t* ib, data_block_t* ob, int print_informati
     }
     /* fresh models (the first block of a file, the dictionary blob, every file of up to one block): the batched kernel
      * pipeline; a block that continues the previous one's models: the model-carrying one-wave coder */
+    uint64_t zero = 0;
+    static uint8_t dummy;
+    if (shim_carry(codec)) {
+        crgpu_ctx* c = fast_ctx("lzencode");
+        if (!c) { data_block_resize(ob, 0); return; }
+        if (!g_fresh && !g_carry_state) { data_block_resize(ob, 0); shim_fail(CRGPU_E_ARG, "lzencode", "the models to continue were left by lzdecode: not in the carried store"); return; }
+        int rc = CRGPU_OK;
+        if (!g_carry_models) rc = crgpu_models_create(c, &g_carry_models);             /* (comes reset) */
+        else if (g_fresh) rc = crgpu_models_reset(c, g_carry_models);
+        data_block_resize(ob, crgpu_bound(codec, n));
+        if (rc == CRGPU_OK) rc = crgpu_encode_blocks_carried(c, codec, g_carry_models, n ? ib->m_data : &dummy, &zero, &n, 1, ob->m_data, &zero, &produced);
+        if (rc != CRGPU_OK || produced == 0xFFFFFFFFu) { data_block_resize(ob, 0); shim_fail(rc != CRGPU_OK ? rc : CRGPU_E_ARG, "lzencode", crgpu_last_error(c)); return; }
+        g_last_shim_ctx = c;
+        g_fresh = 0; g_carry_state = 1;
+        data_block_resize(ob, produced);
+        return;
+    }
     const int fresh = g_fresh && !g_expect_dependent;
     crgpu_ctx* c = fresh ? fast_ctx("lzencode") : carried_ctx("lzencode", codec);
     if (!c) { data_block_resize(ob, 0); return; }
-    uint64_t zero = 0;
     data_block_resize(ob, crgpu_bound(codec, n));
-    static uint8_t dummy;
     int rc = crgpu_encode_blocks(c, codec, n ? ib->m_data : &dummy, &zero, &n, 1, ob->m_data, &zero, &produced);
     if (rc != CRGPU_OK || produced == 0xFFFFFFFFu) { data_block_resize(ob, 0); shim_fail(rc != CRGPU_OK ? rc : CRGPU_E_ARG, "lzencode", crgpu_last_error(c)); return; }
     g_last_shim_ctx = c;
@@ -2581,6 +2769,10 @@ extern "C" void lzdecode(data_block_t* ib, data_block_t* ob, int print_informati
         if (coded || total > 0xFFFFFFFFu - base) { shim_fail(CRGPU_E_ARG, "lzdecode", "block larger than CRGPU_MAX_BLOCK + 1"); return; }
         data_block_resize(ob, base + total);                   /* the stored form lzencode writes for oversized blocks */
         memcpy(ob->m_data + base, ib->m_data + hdr, total);
+        return;
+    }
+    if (shim_carry(codec) && !g_fresh && g_carry_state) {
+        shim_fail(CRGPU_E_ARG, "lzdecode", "the models to continue are in the carried store of lzencode (crgpu_shim_pipeline_carry): dependent blocks decode with the switch off");
         return;
     }
     const int fresh = g_fresh && !g_expect_dependent;

@@ -107,7 +107,10 @@ CR_DEV CrEvViews cr_ev_views(uint8_t* base, uint32_t cap) {
  * at 0 at position 9 (cr-coder.c:143-145) and a literal escape byte enters the context twice
  * (cr-coder.c:186-190); either wears off after a match or a few tokens. */
 #define CR_EVT_BATCH 4u
-CR_DEV void cr_rop_emit_events(const uint8_t* src, uint32_t n, const uint8_t* lens, CrEvViews& V, CrShared& sh) {
+/* ctx_io (crgpu_carry.h): the model's context register lives there — the first tokens take their contexts from it instead of 0
+ * (CARRY) and the call leaves it as the token loop does (ppm_update_context, cr-ppm.c:60-64); a block under 16 bytes does not touch it */
+template <bool CARRY = false>
+CR_DEV void cr_rop_emit_events(const uint8_t* src, uint32_t n, const uint8_t* lens, CrEvViews& V, CrShared& sh, uint32_t* ctx_io = nullptr) {
     const uint32_t lane = cr_lane();
     if (n < 16u) {                                            /* cr-coder.c:140-142 */
         if (lane == 0) { V.ctr[0] = 0; V.ctr[1] = 0; V.ctr[2] = 0; V.ctr[3] = 0x100u; }
@@ -116,6 +119,7 @@ CR_DEV void cr_rop_emit_events(const uint8_t* src, uint32_t n, const uint8_t* le
     const uint32_t esc = cr_pick_escape(src, n, sh.hist);
     uint32_t nev = 0, skip_until = CR_LZP_SKIP;
     uint32_t fixn = 4, fctx = 0;                              /* tokens still to patch, and with what */
+    if constexpr (CARRY) fctx = cr_uni(*ctx_io);
     for (uint32_t base0 = CR_LZP_SKIP; base0 < n; base0 += 64u * CR_EVT_BATCH) {
         uint32_t bc[CR_EVT_BATCH], bl[CR_EVT_BATCH], bx[CR_EVT_BATCH];
 #pragma unroll
@@ -184,6 +188,8 @@ CR_DEV void cr_rop_emit_events(const uint8_t* src, uint32_t n, const uint8_t* le
         }
     }
     if (lane == 0) { V.ctr[0] = nev; V.ctr[1] = 0; V.ctr[2] = 0; V.ctr[3] = esc; }
+    /* behind a match or four plain tokens the register is the block's last four bytes; until then the patch holds it */
+    if constexpr (CARRY) if (lane == 0) *ctx_io = fixn ? fctx : __builtin_bswap32(*reinterpret_cast<const cr_u32u*>(src + n - 4u));
 }
 
 /* ------------------------------------------------------------------ k_rop_links */
@@ -843,9 +849,11 @@ CR_DEV void cr_rop_o2_all(CrEvViews& V, uint8_t* lane_node, uint32_t nchains, ui
  * counts in registers, one word per lane. Rows are taken longest first. Result per escape: the
  * second range-coder triple, stored over the first two words of its exclusion set. */
 #define CR_O1_THREADS CR_SORT_THREADS
-CR_DEV void cr_rop_o1_row(CrEvViews& V, uint32_t* lds_masks /* [64][8] of this wave */, uint32_t at, uint32_t end) {
+/* o1row (crgpu_carry.h): the row's 256 counts in a model store — the row starts from them and is written back */
+CR_DEV void cr_rop_o1_row(CrEvViews& V, uint32_t* lds_masks /* [64][8] of this wave */, uint32_t at, uint32_t end, uint8_t* o1row = nullptr) {
     const uint32_t lane = cr_lane();
     uint32_t row = 0x01010101u;                                          /* ppm_init: every count 1 */
+    if (o1row) row = reinterpret_cast<const uint32_t*>(o1row)[lane];
     /* software pipeline over batches of 64 escapes: while batch b is coded the operands of b+1 load */
     u64 e_next = 0; uint32_t sy_next = 0; u64 tr_next = 0; uint4 m0_next = make_uint4(0, 0, 0, 0), m1_next = m0_next;
     if (at + lane < end) e_next = V.escB[at + lane];
@@ -927,6 +935,7 @@ CR_DEV void cr_rop_o1_row(CrEvViews& V, uint32_t* lds_masks /* [64][8] of this w
         if (lane < cnt) *reinterpret_cast<u64*>(V.mask + (u64)(uint32_t)e_cur * 8u) = res;
         cr_lds_order();
     }
+    if (o1row) reinterpret_cast<uint32_t*>(o1row)[lane] = row;
 }
 
 /* The same row, 64 escapes per wave-step (round 5): lane k = escape k of the batch. Between two halvings a row is a pure
@@ -955,10 +964,11 @@ CR_DEV void cr_o1_ops_load(CrO1Ops& o, const CrEvViews& V, u64 e) {
     o.x0 = mp[0]; o.x1 = mp[1];
     if (empty) { o.x0 = make_uint4(0u, 0u, 0u, 0u); o.x1 = o.x0; }
 }
-CR_DEV void cr_rop_o1_row_batch(CrEvViews& V, uint32_t* lds /* [640] of this wave */, uint32_t at, uint32_t end) {
+CR_DEV void cr_rop_o1_row_batch(CrEvViews& V, uint32_t* lds /* [640] of this wave */, uint32_t at, uint32_t end, uint8_t* o1row = nullptr) {
     const uint32_t lane = cr_lane();
     const u64 below_me = (1ull << lane) - 1ull;
     uint32_t row = 0x01010101u;                                          /* ppm_init: every count 1; lane l byte j = symbol l + 64 j */
+    if (o1row) row = (uint32_t)o1row[lane] | ((uint32_t)o1row[lane + 64u] << 8) | ((uint32_t)o1row[lane + 128u] << 16) | ((uint32_t)o1row[lane + 192u] << 24);
     uint32_t* const my = lds + lane * 9u;
     const uint32_t last = end - 1u;
     /* software pipeline: while a batch is coded the operands of the next one load (and the event numbers of the one after) */
@@ -1086,9 +1096,10 @@ CR_DEV void cr_rop_o1_row_batch(CrEvViews& V, uint32_t* lds /* [640] of this wav
         cr_lds_order();
     }
     if (res_mine) *reinterpret_cast<u64*>(V.mask + (u64)res_ei * 8u) = res;
+    if (o1row) { o1row[lane] = (uint8_t)row; o1row[lane + 64u] = (uint8_t)(row >> 8); o1row[lane + 128u] = (uint8_t)(row >> 16); o1row[lane + 192u] = (uint8_t)(row >> 24); }
 }
 
-CR_DEV void cr_rop_o1_all(CrSortShared& sh, CrEvViews& V, uint32_t* lds_masks, uint32_t nev, uint32_t serial, u64* st = nullptr) {
+CR_DEV void cr_rop_o1_all(CrSortShared& sh, CrEvViews& V, uint32_t* lds_masks, uint32_t nev, uint32_t serial, u64* st = nullptr, uint8_t* o1 = nullptr /* u8[256][256] of a model store */) {
     const uint32_t t = threadIdx.x, w = cr_wave_id(), lane = cr_lane();
     cr_wg_stamp(st, 12);
     /* 1: the escapes, in coding order; wave w owns a contiguous quarter of the events */
@@ -1161,8 +1172,9 @@ CR_DEV void cr_rop_o1_all(CrSortShared& sh, CrEvViews& V, uint32_t* lds_masks, u
         if (len == 0u) break;                                             /* rows are sorted by length */
         /* rows of a dozen escapes and more in batches of 64 (a batch costs what ~8 escapes of the serial loop cost) */
         const u64 row_t0 = st ? __builtin_amdgcn_s_memrealtime() : 0;
-        if (serial || len < 12u) cr_rop_o1_row(V, lds_masks + w * CR_O1_LDS_PER_WAVE, s0, s0 + len);
-        else cr_rop_o1_row_batch(V, lds_masks + w * CR_O1_LDS_PER_WAVE, s0, s0 + len);
+        uint8_t* const o1row = o1 ? o1 + r * 256u : nullptr;
+        if (serial || len < 12u) cr_rop_o1_row(V, lds_masks + w * CR_O1_LDS_PER_WAVE, s0, s0 + len, o1row);
+        else cr_rop_o1_row_batch(V, lds_masks + w * CR_O1_LDS_PER_WAVE, s0, s0 + len, o1row);
         if (st && k == 0 && lane == 0) st[9] = __builtin_amdgcn_s_memrealtime() - row_t0;   /* the longest row alone (100 MHz ticks) */
     }
     __syncthreads();

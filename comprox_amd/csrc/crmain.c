@@ -579,6 +579,7 @@ int main(int argc, char** argv) {
             mark("gpu_contexts_closed");
         } else {
             crgpu_shim_expect_dependent_blocks(size > opt_block);      /* several blocks: they continue each other's models */
+            crgpu_shim_pipeline_carry(1);                              /* comprop: ... on the kernel pipeline, the models in a device store (no effect on the other two codecs) */
             rc = encode_sequential(src, dst);
         }
     } else {

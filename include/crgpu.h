@@ -115,6 +115,28 @@ int crgpu_decode_blocks_dev(crgpu_ctx* ctx, int codec,
                             uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
                             uint32_t* out_size, int sync);
 
+/* comprop with models that outlive the block: the reference's ppm_model_t (src/cr-ppm.h:36-41) survives from one lzencode to
+ * the next until reset_models(), and the stock container codes every file larger than one block that way. A crgpu_models
+ * holds that state in device memory (26 280 192 bytes, and as much again for the copy the abort point goes back to),
+ * indexed by the reference's own keys; create leaves it in the ppm_model_init state, reset puts it back there (enqueued on
+ * the context's stream). It belongs to the context it was created on. */
+typedef struct crgpu_models crgpu_models;
+int  crgpu_models_create(crgpu_ctx* ctx, crgpu_models** out);
+void crgpu_models_destroy(crgpu_models* m);
+int  crgpu_models_reset(crgpu_ctx* ctx, crgpu_models* m);
+/* Pointer conventions of crgpu_encode_blocks_dev. Block 0 starts from the state in `m`, block i continues block i - 1, and on
+ * return `m` holds the state behind the last block — a block that ends stored leaves it where lzencode gave up
+ * (src/ropmain/cr-coder.c:204-206), one under 16 bytes does not touch it. Every block's bytes are what the reference's lzencode
+ * writes for it in that sequence. codec must be CRGPU_CODEC_ROP (CRGPU_E_ARG otherwise: comprox and comprolz carry side models
+ * too). The call returns when the blocks are coded. */
+int crgpu_encode_blocks_carried_dev(crgpu_ctx* ctx, int codec, crgpu_models* m,
+                                    const uint8_t* in, const uint64_t* in_off, const uint32_t* in_size, uint32_t nblocks,
+                                    uint8_t* out, const uint64_t* out_off, uint32_t* out_size);
+/* ... and with HOST pointers (the conventions of crgpu_encode_blocks) */
+int crgpu_encode_blocks_carried(crgpu_ctx* ctx, int codec, crgpu_models* m,
+                                const uint8_t* in, const uint64_t* in_off, const uint32_t* in_size, uint32_t nblocks,
+                                uint8_t* out, const uint64_t* out_off, uint32_t* out_size);
+
 /* Device-side concatenation of a batch (`k_pack`; the write loop of src/main.c:198-205 as one contiguous run):
  * payload b = in[in_off[b] .. +in_size[b]) is copied to out[out_off[b] ..) where out_off is the exclusive sum of the
  * slots in front of it. with_headers != 0: every non-empty block is preceded by the container's packed
@@ -290,6 +312,12 @@ int  crgpu_shim_prepare(void);
  * src/main.c:174-206). A block that starts from fresh models then runs on the model-carrying coder at once, so that its
  * successor continues from its models instead of rebuilding them from a second pass over its input. Same bytes either way. */
 void crgpu_shim_expect_dependent_blocks(int on);
+/* Opt-in (also: CRGPU_SHIM_PIPELINE_CARRY=1 in the environment, read at the first shim call): comprop's lzencode runs every
+ * block through crgpu_encode_blocks_carried with one process-wide crgpu_models, whether the block starts fresh or continues the
+ * last one; reset_models() resets the store; no input is remembered or replayed. An lzdecode that would have to continue
+ * models the store holds reports CRGPU_E_ARG through the error hook (decoding dependent blocks stays on the one-wave coder:
+ * leave the switch off in a process that does both). Off, the default: nothing changes. */
+void crgpu_shim_pipeline_carry(int on);
 float crgpu_shim_last_kernel_ms(void);                /* kernel time of the most recent lzencode / lzdecode call, -1 if none */
 /* Page-locked host memory for buffers handed to the host-pointer entry points (DMA at the link's rate instead of the
  * runtime's staging of pageable memory); release with crgpu_host_free. NULL when it cannot be had. */

@@ -1,0 +1,156 @@
+"""GPU tests of comprop's kernel pipeline on carried models (crgpu_models, crgpu_encode_blocks_carried*, crgpu_carry.h): a run
+of dependent blocks must come out byte for byte as the reference's lzencode writes it when reset_models() is called in front
+of the first block only (the oracle with reset=(b == 0)), and must decode back through the model-carrying decoder — as far as
+the format allows: see the note at the decode check."""
+import ctypes
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import crlib
+from comprox_amd import api
+
+pytestmark = pytest.mark.gpu
+
+T = crlib.gen_text
+_t3 = T(12288, 41)
+A, B, C = _t3[:4096], _t3[4096:8192], _t3[8192:]
+_o1 = [bytes([x, 0x6E, 0x21]) for x in range(256)]           # 256 contexts (x, 'n') that all escape to '!' in row 'n'
+_n62 = [bytes([65, 66, s]) for s in range(100, 190)]          # context "AB" meets 90 different bytes
+CASES = [
+    ("text3", [A, B, C]),                                     # nodes, order-3 entries and rows all met again
+    ("repeat", [A, B, B]),                                    # carried predictions are right from the first event
+    ("o2_halving", [b"ab" * 180, b"ab" * 180]),               # count(256) of "ab" / "ba" passes 250 in block 2 only with block 1's hits
+    ("o1_255", [b"".join(_o1[:130]), b"".join(_o1[130:])]),   # row 'n', byte '!': 1 + 254 escapes = 255 in block 2
+    ("node62", [b"".join(_n62[:45]), b"".join(_n62[45:])]),   # a node that passes 62 symbols across the boundary
+    ("tiny_between", [A, b"", B[:15], C]),                    # under 16 bytes: models and context untouched
+    ("stored_between", [A, crlib.gen_rand(2048, seed=9), B]),  # ends stored: the models stay at the abort point
+    ("families", [T(20000, 42), T(40000, 43), T(70000, 44)]),  # 28 KiB LDS kernels, the lds64 kernels, table sweeps + ticket walkers
+]
+
+
+def _boundary_cases(oracle):
+    """blocks whose coded size sits at the stored rule's boundary (one byte either side of the flip), each followed by text"""
+    return [("boundary%d" % k, [blk, B]) for k, blk in
+            enumerate(crlib.gen_stored_boundary(oracle.rop_encode, sizes=((1200, 1),), around=1))]
+
+
+def _expect(oracle, blocks):
+    return [oracle.rop_encode(b, reset=(i == 0)) for i, b in enumerate(blocks)]
+
+
+def _encode_dev(gpu, models, blocks):
+    import torch
+    sizes = np.array([len(b) for b in blocks], dtype=np.uint32)
+    in_off = np.concatenate(([0], np.cumsum(sizes[:-1], dtype=np.uint64))).astype(np.uint64)
+    caps = sizes.astype(np.uint64) + 20
+    out_off = np.concatenate(([0], np.cumsum(caps[:-1], dtype=np.uint64))).astype(np.uint64)
+    dev = lambda a: torch.from_numpy(a.view(np.uint8).copy()).cuda()        # noqa: E731
+    d_in = dev(np.frombuffer(b"".join(blocks) + b"\0", dtype=np.uint8))
+    d_io, d_sz, d_oo = dev(in_off), dev(sizes), dev(out_off)
+    d_out = torch.zeros(int(caps.sum()), dtype=torch.uint8, device="cuda")
+    d_os = torch.zeros(len(blocks) * 4, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    gpu.encode_blocks_carried_dev(models, d_in.data_ptr(), d_io.data_ptr(), d_sz.data_ptr(), len(blocks),
+                                  d_out.data_ptr(), d_oo.data_ptr(), d_os.data_ptr())
+    got, out = d_os.cpu().numpy().view(np.uint32), d_out.cpu().numpy()
+    return [out[int(o):int(o) + int(s)].tobytes() for o, s in zip(out_off, got)]
+
+
+def shim_call(L, fn, data):
+    """fn = the library's lzencode / lzdecode shim on one data_block_t"""
+    ib, ob = api.DataBlock(), api.DataBlock()
+    L.data_block_resize(ctypes.byref(ib), len(data))
+    if len(data):
+        ctypes.memmove(ib.m_data, bytes(data), len(data))
+    fn(ctypes.byref(ib), ctypes.byref(ob), 0)
+    out = ctypes.string_at(ob.m_data, ob.m_size) if ob.m_size else b""
+    L.data_block_destroy(ctypes.byref(ib))
+    L.data_block_destroy(ctypes.byref(ob))
+    return out
+
+
+def _decode_carried(blocks):
+    """the library's lzdecode shim on its model-carrying context: reset_models() once, then block after block"""
+    L = api.load_library()
+    L.crgpu_shim_config(api.CODEC_ROP, 0)
+    L.crgpu_shim_pipeline_carry(0)
+    L.reset_models()
+    return [shim_call(L, L.lzdecode, b) for b in blocks]
+
+
+@pytest.mark.parametrize("tables", [0, 1], ids=["lds", "tables"])
+@pytest.mark.parametrize("name", [c[0] for c in CASES] + ["boundary0", "boundary1", "boundary2", "reset_mid", "dev"])
+def test_carried_blocks_equal_the_reference_sequence(gpu, oracle, name, tables):
+    blocks = dict(CASES + _boundary_cases(oracle) + [("reset_mid", [A, B]), ("dev", [A, b"", crlib.gen_rand(2048, seed=9), B, T(30000, 45)])])[name]
+    want = _expect(oracle, blocks)
+    models = gpu.models_create()
+    gpu.set_option(api.OPT_LZP_TABLES, tables)
+    try:
+        if name == "dev":
+            got = _encode_dev(gpu, models, blocks)
+        else:
+            got = gpu.encode_blocks(blocks, models=models)                 # the host twin
+        if name == "reset_mid":                                            # crgpu_models_reset in mid-sequence = a new sequence
+            assert gpu.encode_blocks([blocks[1]], models=models) != [want[1]]
+            models.reset()
+            assert gpu.encode_blocks(blocks, models=models) == want
+    finally:
+        gpu.set_option(api.OPT_LZP_TABLES, 0)
+        models.close()
+    for i, (g, w) in enumerate(zip(got, want)):
+        assert g == w, f"{name}: block {i} of {len(blocks)} differs ({len(g)} bytes, expected {len(w)})"
+    if name in ("stored_between", "boundary1", "boundary2"):
+        assert any(w[0] == 0 and len(b) >= 16 for w, b in zip(want, blocks)), "the case is meant to hold a block that ends stored"
+    if tables == 0:
+        # lzdecode copies a stored block and leaves the models alone (cr-coder.c:243-248) while lzencode kept what it had
+        # learnt up to the abort point: behind a stored block of 16 bytes or more no decoder of the format follows the
+        # encoder's models, the reference's included. The sequence decodes up to and including the first such block.
+        stored = [i for i, (w, b) in enumerate(zip(want, blocks)) if w[0] == 0 and len(b) >= 16]
+        upto = stored[0] + 1 if stored else len(blocks)
+        assert _decode_carried(got[:upto]) == [bytes(b) for b in blocks[:upto]]
+
+
+def test_other_codecs_are_refused(gpu):
+    models = gpu.models_create()
+    try:
+        for codec in (api.CODEC_ROX, api.CODEC_ROLZ):
+            with pytest.raises(Exception, match="-2"):
+                gpu.encode_blocks([A], codec=codec, models=models)
+    finally:
+        models.close()
+
+
+CHILD = r"""
+import ctypes, json, sys
+sys.path[:0] = [%r, %r]
+from comprox_amd import api
+from test_gpu_carry import shim_call
+L = api.load_library()
+HANDLER = ctypes.CFUNCTYPE(None, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p)
+seen = []
+cb = HANDLER(lambda code, msg, user: seen.append(code))
+L.crgpu_shim_set_error_handler.argtypes = [HANDLER, ctypes.c_void_p]
+L.crgpu_shim_set_error_handler(cb, None)
+blocks = [bytes.fromhex(h) for h in json.load(sys.stdin)]
+L.reset_models()
+out = [shim_call(L, L.lzencode, b).hex() for b in blocks]
+errs = list(seen)
+back = shim_call(L, L.lzdecode, bytes.fromhex(out[0]))
+print(json.dumps({"out": out, "encode_errors": errs, "decode_errors": seen[len(errs):], "decoded": len(back)}))
+"""
+
+
+def test_shim_opt_in_by_environment(gpu, oracle):
+    blocks = [A, B, C]
+    env = dict(os.environ, CRGPU_SHIM_PIPELINE_CARRY="1")
+    r = subprocess.run([sys.executable, "-c", CHILD % (crlib.ROOT, os.path.dirname(os.path.abspath(__file__)))], env=env,
+                       input=json.dumps([b.hex() for b in blocks]), capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    res = json.loads(r.stdout.strip().splitlines()[-1])
+    assert [bytes.fromhex(h) for h in res["out"]] == _expect(oracle, blocks) and res["encode_errors"] == []
+    assert res["decode_errors"] == [-2] and res["decoded"] == 0           # CRGPU_E_ARG through the hook, no crash
