@@ -105,6 +105,16 @@ def load_library():
     L.crgpu_encode_blocks_carried_dev.argtypes = [vp, i32, vp, vp, vp, vp, u32, vp, vp, vp]
     L.crgpu_encode_blocks_carried.restype = i32
     L.crgpu_encode_blocks_carried.argtypes = [vp, i32, vp, vp, vp, vp, u32, vp, vp, vp]
+    L.crgpu_model_set_create.restype = i32
+    L.crgpu_model_set_create.argtypes = [vp, u32, u32, ctypes.POINTER(vp)]
+    L.crgpu_model_set_destroy.restype = None
+    L.crgpu_model_set_destroy.argtypes = [vp]
+    L.crgpu_model_set_reset.restype = i32
+    L.crgpu_model_set_reset.argtypes = [vp, vp, vp, u32]
+    L.crgpu_encode_sequences_carried_dev.restype = i32
+    L.crgpu_encode_sequences_carried_dev.argtypes = [vp, i32, vp, vp, vp, vp, vp, u32, vp, vp, vp]
+    L.crgpu_encode_sequences_carried.restype = i32
+    L.crgpu_encode_sequences_carried.argtypes = [vp, i32, vp, vp, vp, vp, vp, u32, vp, vp, vp]
     L.crgpu_shim_pipeline_carry.restype = None
     L.crgpu_shim_pipeline_carry.argtypes = [i32]
     L.crgpu_dict_create.restype = i32
@@ -331,6 +341,44 @@ class CrGpu:
     def models_create(self) -> "CrModels":
         return CrModels(self)
 
+    def model_set_create(self, nseq: int, max_block: int) -> "CrModelSet":
+        return CrModelSet(self, nseq, max_block)
+
+    def encode_sequences(self, sequences, model_set: "CrModelSet", codec: int = CODEC_ROP):
+        """sequences: list of lists of bytes-like, sequence s on slot s of the set. Block t of every sequence is coded in one
+        pass of the pipeline; within a sequence every block continues the one before, the first one the slot's state.
+        Returns the encoded bytes in the same shape."""
+        blocks = [b for seq in sequences for b in seq]
+        seq_first = np.zeros(len(sequences) + 1, dtype=np.uint32)
+        seq_first[1:] = np.cumsum([len(seq) for seq in sequences], dtype=np.uint64)
+        return self._encode_sequences_flat(blocks, seq_first, model_set, codec)
+
+    def _encode_sequences_flat(self, blocks, seq_first, model_set, codec=CODEC_ROP):
+        nb = len(blocks)
+        sizes = np.array([len(b) for b in blocks] or [0], dtype=np.uint32)
+        in_off = np.zeros(len(sizes), dtype=np.uint64)
+        in_off[1:] = np.cumsum(sizes[:-1], dtype=np.uint64)
+        src = np.frombuffer(b"".join(bytes(b) for b in blocks) or b"\0", dtype=np.uint8)
+        caps = np.array([bound(codec, int(x)) for x in sizes], dtype=np.uint64)
+        out_off = np.zeros(len(sizes), dtype=np.uint64)
+        out_off[1:] = np.cumsum(caps[:-1], dtype=np.uint64)
+        out = np.zeros(int(caps.sum()), dtype=np.uint8)
+        out_size = np.zeros(len(sizes), dtype=np.uint32)
+        seq_first = np.ascontiguousarray(seq_first, dtype=np.uint32)
+        self._check(self.lib.crgpu_encode_sequences_carried(self.h, codec, model_set.h, _ptr(src), _ptr(in_off), _ptr(sizes), _ptr(seq_first),
+                                                            len(seq_first) - 1, _ptr(out), _ptr(out_off), _ptr(out_size)),
+                    "crgpu_encode_sequences_carried")
+        coded = [out[int(o):int(o) + int(s)].tobytes() for o, s in zip(out_off[:nb], out_size[:nb])]
+        return [coded[int(a):int(b)] for a, b in zip(seq_first[:-1], seq_first[1:])]
+
+    def encode_sequences_carried_dev(self, model_set, d_in, d_in_off, d_in_size, seq_first, d_out, d_out_off, d_out_size,
+                                     codec=CODEC_ROP):
+        """The same with everything in device memory except seq_first (host: a sequence of len(sequences) + 1 ints)."""
+        seq_first = np.ascontiguousarray(seq_first, dtype=np.uint32)
+        self._check(self.lib.crgpu_encode_sequences_carried_dev(self.h, codec, model_set.h, d_in, d_in_off, d_in_size, _ptr(seq_first),
+                                                                len(seq_first) - 1, d_out, d_out_off, d_out_size),
+                    "crgpu_encode_sequences_carried_dev")
+
     def decode_blocks_dev(self, codec, d_in, d_in_off, d_in_size, nblocks, max_block, d_out, d_out_off, d_out_cap,
                           d_out_size, sync=False):
         self._check(self.lib.crgpu_decode_blocks_dev(self.h, codec, d_in, d_in_off, d_in_size, nblocks, max_block,
@@ -517,6 +565,35 @@ class CrModels:
     def close(self):
         if self.h:
             self.gpu.lib.crgpu_models_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CrModelSet:
+    """`nseq` stores of comprop's PPM models with their undo logs (crgpu_model_set), one slot per sequence of dependent blocks."""
+
+    def __init__(self, gpu: CrGpu, nseq: int, max_block: int):
+        self.gpu = gpu
+        self.nseq = nseq
+        self.h = ctypes.c_void_p()
+        gpu._check(gpu.lib.crgpu_model_set_create(gpu.h, nseq, max_block, ctypes.byref(self.h)), "crgpu_model_set_create")
+
+    def reset(self, which=None):
+        """every slot, or the slots listed in `which`, back to the state of reset_models()"""
+        w = None if which is None else np.array(list(which), dtype=np.uint32)
+        if w is not None and len(w) == 0:
+            return
+        self.gpu._check(self.gpu.lib.crgpu_model_set_reset(self.gpu.h, self.h, None if w is None else _ptr(w), 0 if w is None else len(w)),
+                        "crgpu_model_set_reset")
+
+    def close(self):
+        if self.h:
+            self.gpu.lib.crgpu_model_set_destroy(self.h)
             self.h = ctypes.c_void_p()
 
     def __del__(self):

@@ -12,6 +12,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 
 #include "../../include/crgpu.h"
 #include "crgpu_rop.h"
@@ -27,6 +28,7 @@
 #include "crgpu_lzp2.h"
 #include "crgpu_links2.h"
 #include "crgpu_carry.h"
+#include "crgpu_seq.h"
 #include "crgpu_rolz3.h"
 #include "crgpu_rox3.h"
 #include "crgpu_dicpick.h"
@@ -1728,6 +1730,237 @@ extern "C" int crgpu_encode_blocks_carried_dev(crgpu_ctx* c, int codec, crgpu_mo
     return rc;
 }
 
+/* ------------------------------------------------------------------ many sequences in lockstep (crgpu_seq.h) */
+
+struct crgpu_model_set {
+    crgpu_ctx* ctx;
+    uint32_t   nseq, max_block, ev_cap;
+    uint8_t*   d_store;                    /* nseq x CR_M_BYTES */
+    uint8_t*   d_log;                      /* nseq x log_stride: the undo logs */
+    u64        log_stride, off_log3;
+    uint32_t*  d_idx;                      /* 3 x nseq words: a call's slot per internal sequence, a reset's list, the order-2 chain counters */
+    uint8_t*   d_desc; size_t desc_cap;    /* a call's step-major block descriptors */
+};
+
+static uint32_t seq_ev_cap(uint32_t max_block) { return (uint32_t)align_up((u64)(max_block < 1024u ? 1024u : max_block) + max_block / 64u + 128u, 64); }
+
+extern "C" int crgpu_model_set_reset(crgpu_ctx* c, crgpu_model_set* m, const uint32_t* which, uint32_t n) {
+    if (!c || !m || m->ctx != c) return CRGPU_E_ARG;
+    CR_TRY(c, hipSetDevice(c->device));
+    const uint32_t grid = (uint32_t)c->num_cu * 4u;
+    if (!which) {
+        crs_launch_fill(c->stream, grid, m->d_store, NULL, m->nseq);
+        CR_TRY(c, hipGetLastError());
+        return CRGPU_OK;
+    }
+    if (n == 0) return CRGPU_OK;
+    if (n > m->nseq) { snprintf(c->err, sizeof c->err, "%u slots to reset, the set has %u", n, m->nseq); return CRGPU_E_ARG; }
+    for (uint32_t i = 0; i < n; i++) if (which[i] >= m->nseq) { snprintf(c->err, sizeof c->err, "slot %u of a set of %u", which[i], m->nseq); return CRGPU_E_ARG; }
+    CR_TRY(c, hipMemcpyAsync(m->d_idx + m->nseq, which, 4u * n, hipMemcpyHostToDevice, c->stream));
+    crs_launch_fill(c->stream, grid, m->d_store, m->d_idx + m->nseq, n);
+    CR_TRY(c, hipGetLastError());
+    CR_TRY(c, hipStreamSynchronize(c->stream));          /* (the list is the caller's memory, and the next reset's list goes to the same place) */
+    return CRGPU_OK;
+}
+
+extern "C" void crgpu_model_set_destroy(crgpu_model_set* m) {
+    if (!m) return;
+    (void)hipSetDevice(m->ctx->device);
+    (void)hipStreamSynchronize(m->ctx->stream);
+    (void)hipFree(m->d_store); (void)hipFree(m->d_log); (void)hipFree(m->d_idx); (void)hipFree(m->d_desc);
+    free(m);
+}
+
+extern "C" int crgpu_model_set_create(crgpu_ctx* c, uint32_t nseq, uint32_t max_block, crgpu_model_set** out) {
+    if (!c || !out) return CRGPU_E_ARG;
+    *out = NULL;
+    if (nseq == 0 || nseq > 65535u || max_block > CRGPU_MAX_BLOCK + 1u) { snprintf(c->err, sizeof c->err, "a model set has 1 .. 65535 slots for blocks of up to CRGPU_MAX_BLOCK + 1 bytes"); return CRGPU_E_ARG; }
+    CR_TRY(c, hipSetDevice(c->device));
+    crgpu_model_set* m = (crgpu_model_set*)calloc(1, sizeof *m);
+    if (!m) return CRGPU_E_NOMEM;
+    m->ctx = c; m->nseq = nseq; m->max_block = max_block; m->ev_cap = seq_ev_cap(max_block);
+    const u64 n2 = m->ev_cap < 65536u ? m->ev_cap : 65536u, n3 = m->ev_cap < (1u << 22) ? m->ev_cap : (1u << 22);
+    m->off_log3 = CR_SEQ_LOG1_BYTES + (u64)CR_SEQ_LOG2_REC * n2;
+    m->log_stride = m->off_log3 + 8u * n3;               /* (a multiple of 16: ev_cap is one of 64) */
+    if (hipMalloc((void**)&m->d_store, (size_t)(nseq * CR_M_BYTES)) != hipSuccess || hipMalloc((void**)&m->d_log, (size_t)(nseq * m->log_stride)) != hipSuccess ||
+        hipMalloc((void**)&m->d_idx, (size_t)nseq * 12u) != hipSuccess) {
+        (void)hipGetLastError();
+        snprintf(c->err, sizeof c->err, "hipMalloc(model set, %u x (%llu + %llu) bytes) failed", nseq, (unsigned long long)CR_M_BYTES, (unsigned long long)m->log_stride);
+        crgpu_model_set_destroy(m);
+        return CRGPU_E_NOMEM;
+    }
+    const int rc = crgpu_model_set_reset(c, m, NULL, 0);
+    if (rc != CRGPU_OK) { crgpu_model_set_destroy(m); return rc; }
+    *out = m;
+    return CRGPU_OK;
+}
+
+/* the events of the launch's blocks -> triples: the sorts of crgpu.hip on the sub-batch, then one launch each of the
+ * slot-backed chain kernels. The workgroups a block's chains get shrink as the active blocks grow: the chip is filled by
+ * blocks x workgroups, and a block's share beyond that only queues */
+static int seq_chain_stages(crgpu_ctx* c, CrBatch B, const CrArenaLayout& LY, const CrSeq& Q, uint32_t maxn, uint32_t grid, int lds) {
+    B.links_lds = lds && !c->lzp_tables_only ? 1u : 0u;
+    B.o2_tickets = c->lzp_tables_only ? 1u : 0u;
+    CR_TRY(c, hipMemsetAsync(c->ticket, 0, 128, c->stream));
+    if (B.links_lds) {
+        if (!c->links_lds_ready) {
+            CR_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_rop_links_lds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)CR_LZ2_LDS_BYTES));
+            CR_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_rop_links_lds64), hipFuncAttributeMaxDynamicSharedMemorySize, (int)CR_LK4_LDS_BYTES));
+            c->links_lds_ready = 1;
+        }
+        const uint32_t lg = (uint32_t)c->num_cu < grid ? (uint32_t)c->num_cu : grid;
+        CR_CARRY_STAGE("k_rop_links_lds", hipLaunchKernelGGL(k_rop_links_lds, dim3(lg), dim3(CR_LZ2_THREADS), CR_LZ2_LDS_BYTES, c->stream, B, LY));
+        if (maxn > CR_LZ2_MAXN / 2u) CR_CARRY_STAGE("k_rop_links_lds64", hipLaunchKernelGGL(k_rop_links_lds64, dim3(lg), dim3(CR_LK4_THREADS), CR_LK4_LDS_BYTES, c->stream, B, LY));
+    }
+    CR_CARRY_STAGE("k_rop_links", hipLaunchKernelGGL(k_rop_links, CR_G(k_rop_links, CR_SORT_THREADS, 0), dim3(CR_SORT_THREADS), 0, c->stream, B, LY));
+    const uint32_t cus = (uint32_t)c->num_cu;
+    uint32_t g3 = maxn / 16384u + 1u, g2 = maxn / 2048u + 1u;
+    if (g3 > cus * 4u / B.nblocks) g3 = cus * 4u / B.nblocks;
+    if (g2 > cus * 8u / B.nblocks) g2 = cus * 8u / B.nblocks;
+    CR_CARRY_STAGE("k_seq_o3", crs_launch_o3(c->stream, g3 ? g3 : 1u, B, Q));
+    CR_CARRY_STAGE("k_seq_o2", crs_launch_o2(c->stream, g2 ? g2 : 1u, B, Q));
+    CR_CARRY_STAGE("k_seq_o1", crs_launch_o1(c->stream, B, Q));
+    return CRGPU_OK;
+}
+
+/* one step: block t of every sequence that has one — B holds the step's `B.nblocks` blocks, h_n their sizes, scratch slot j
+ * and Q.slot[j] (= h_slot[j]) belong to the j-th sequence of the internal order. One readback of the sizes is the step's only host wait;
+ * a block that ended stored (rare) then goes back through the undo log, one block at a time */
+static int seq_step(crgpu_ctx* c, CrBatch B, const CrArenaLayout& LY, const CrSeq& Q, const uint32_t* h_slot, const uint32_t* h_n, uint32_t* h_got, uint32_t grid) {
+    const uint32_t na = B.nblocks;
+    uint32_t maxn = 0;
+    for (uint32_t j = 0; j < na; j++) if (h_n[j] > maxn) maxn = h_n[j];
+    CR_TRY(c, hipMemsetAsync(c->ticket, 0, 128, c->stream));
+    CR_TRY(c, hipMemsetAsync(B.pre_done, 0, na, c->stream));
+    CR_CARRY_RC(carry_group_open(c));
+    B.lzp_lds = 0;
+    if (!c->lzp_tables_only) {
+        if (!c->lzp_lds_ready) {
+            CR_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_rop_lzp_lds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)CR_LZ2_LDS_BYTES));
+            c->lzp_lds_ready = 1;
+        }
+        B.lzp_lds = 1;
+        const uint32_t lg = (uint32_t)c->num_cu < grid ? (uint32_t)c->num_cu : grid;
+        CR_CARRY_STAGE("k_rop_lzp_lds", hipLaunchKernelGGL(k_rop_lzp_lds, dim3(lg), dim3(CR_LZ2_THREADS), CR_LZ2_LDS_BYTES, c->stream, B, LY));
+        if (maxn > CR_LZ2_MAXN) {
+            if (!c->lzp64_ready) {
+                CR_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_rop_lzp_lds64), hipFuncAttributeMaxDynamicSharedMemorySize, (int)CR_LZ3_LDS_BYTES));
+                c->lzp64_ready = 1;
+            }
+            CR_CARRY_STAGE("k_rop_lzp_lds64", hipLaunchKernelGGL(k_rop_lzp_lds64, dim3(lg), dim3(CR_LZ2_THREADS), CR_LZ3_LDS_BYTES, c->stream, B, LY));
+        }
+    }
+    CR_CARRY_STAGE("k_rop_lzp", hipLaunchKernelGGL(k_rop_lzp, dim3(grid), dim3(256), 0, c->stream, B, LY));
+    CR_CARRY_STAGE("k_seq_events", crs_launch_events(c->stream, B, LY, Q));
+    CR_CARRY_RC(seq_chain_stages(c, B, LY, Q, maxn, grid, 1));
+    CR_CARRY_STAGE("k_rop_rc", hipLaunchKernelGGL(k_rop_rc, CR_G(k_rop_rc, CRGPU_WAVE, 0), dim3(CRGPU_WAVE), 0, c->stream, B, LY));
+    CR_CARRY_RC(carry_group_close(c));
+    CR_TRY(c, hipMemcpyAsync(h_got, B.out_size, 4u * na, hipMemcpyDeviceToHost, c->stream));
+    CR_TRY(c, hipStreamSynchronize(c->stream));
+    for (uint32_t j = 0; j < na; j++) {
+        /* cr-coder.c:204-206, 218-228: the models stay as they stood at the token where lzencode gave the block up */
+        if (h_n[j] < 16u || h_got[j] != h_n[j] + CRGPU_ROP_HEADER) continue;
+        CrBatch B1 = B;
+        B1.in_off += j; B1.in_size += j; B1.out_off += j; B1.out_size += j; B1.nblocks = 1;
+        B1.ev += (u64)j * B.ev_stride; B1.lens += (u64)j * B.lens_stride; B1.pre_done += j;
+        CrSeq Q1 = Q;
+        Q1.slot += j; Q1.chain_ctr += j;
+        CR_CARRY_RC(carry_group_open(c));
+        CR_CARRY_STAGE("k_seq_undo", crs_launch_undo(c->stream, B1, Q1));
+        CR_CARRY_STAGE("k_ropc_abort", crc_launch_abort(c->stream, B1, Q.store + (u64)h_slot[j] * CR_M_BYTES));
+        CR_CARRY_RC(seq_chain_stages(c, B1, LY, Q1, h_n[j], 1u, 0));
+        CR_CARRY_RC(carry_group_close(c));
+    }
+    return CRGPU_OK;
+}
+
+/* Sequence s owns blocks seq_first[s] .. seq_first[s + 1] - 1 (seq_first in HOST memory, everything else on the device) and
+ * slot s of the set: its first block starts from the slot's state, block i continues block i - 1, the slot keeps what the
+ * last block leaves; a sequence without a block leaves its slot alone. Every block's bytes are what the reference's lzencode
+ * writes for it in its sequence. Returns when all blocks are coded. */
+extern "C" int crgpu_encode_sequences_carried_dev(crgpu_ctx* c, int codec, crgpu_model_set* m, const uint8_t* in, const uint64_t* in_off,
+                                                  const uint32_t* in_size, const uint32_t* seq_first, uint32_t nseq,
+                                                  uint8_t* out, const uint64_t* out_off, uint32_t* out_size) {
+    if (!c || !m || m->ctx != c || (nseq && !seq_first)) return CRGPU_E_ARG;
+    if (codec != CRGPU_CODEC_ROP) { snprintf(c->err, sizeof c->err, "models are carried for comprop only (codec %d)", codec); return CRGPU_E_ARG; }
+    if (c->persist || c->one_wave_encoder) { snprintf(c->err, sizeof c->err, "carried models run on the kernel pipeline: not on a one-wave context"); return CRGPU_E_ARG; }
+    if (nseq > m->nseq) { snprintf(c->err, sizeof c->err, "%u sequences for a set of %u slots", nseq, m->nseq); return CRGPU_E_ARG; }
+    for (uint32_t s = 0; s < nseq; s++) if (seq_first[s + 1u] < seq_first[s]) { snprintf(c->err, sizeof c->err, "seq_first descends at sequence %u", s); return CRGPU_E_ARG; }
+    const uint32_t first = nseq ? seq_first[0] : 0u, nb = nseq ? seq_first[nseq] - first : 0u;
+    if (nb == 0) return CRGPU_OK;
+    if (!in || !in_off || !in_size || !out || !out_off || !out_size) return CRGPU_E_ARG;
+    CR_TRY(c, hipSetDevice(c->device));
+    /* host tables: the callers' sizes, the internal order (by block count, descending: the active set of a step is a
+     * prefix), the step-major map and sizes, a step's sizes read back */
+    uint32_t* h = (uint32_t*)malloc(sizeof(uint32_t) * ((size_t)nb * 3u + (size_t)nseq * 2u));
+    if (!h) return CRGPU_E_NOMEM;
+    uint32_t* const h_size = h, * const h_map = h + nb, * const h_n = h_map + nb, * const h_perm = h_n + nb, * const h_got = h_perm + nseq;
+    int rc = CRGPU_OK;
+    hipError_t e = hipMemcpyAsync(h_size, in_size + first, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { free(h); return fail(c, e, "hipMemcpyAsync(block sizes)"); }
+    for (uint32_t b = 0; b < nb; b++) if (h_size[b] > m->max_block) {
+        snprintf(c->err, sizeof c->err, "block of %u bytes, the model set was made for %u", h_size[b], m->max_block);
+        free(h); return CRGPU_E_ARG;
+    }
+    for (uint32_t s = 0; s < nseq; s++) h_perm[s] = s;
+    std::stable_sort(h_perm, h_perm + nseq, [seq_first](uint32_t a, uint32_t b) { return seq_first[a + 1u] - seq_first[a] > seq_first[b + 1u] - seq_first[b]; });
+    const uint32_t steps = seq_first[h_perm[0] + 1u] - seq_first[h_perm[0]];
+    uint32_t na0 = 0, p = 0;
+    for (uint32_t t = 0; t < steps; t++)
+        for (uint32_t j = 0; j < nseq && seq_first[h_perm[j] + 1u] - seq_first[h_perm[j]] > t; j++) {
+            h_map[p] = seq_first[h_perm[j]] + t;
+            h_n[p] = h_size[h_map[p] - first];
+            p++;
+            if (t == 0) na0++;
+        }
+    uint32_t want = (uint32_t)c->num_cu * (uint32_t)c->wg_per_cu;
+    if (want > na0) want = na0;
+    rc = ensure_arena(c, CR_AR_ENC, m->max_block, want, CR_USE_LZ2 | CR_USE_LZP | CR_USE_CAND);
+    const crgpu_ctx::arena_set* A = &c->arenas[CR_AR_ENC];
+    CrBatch B; memset(&B, 0, sizeof B);
+    B.in = in; B.out = out;
+    B.ticket = c->ticket; B.arena = A->p; B.fresh = 1;
+    B.ev_cap = m->ev_cap;
+    B.ev_stride = align_up(cr_ev_slot_bytes_host(B.ev_cap), 256);
+    B.lens_stride = align_up(m->max_block < 1024u ? 1024u : m->max_block, 256);
+    /* per-block scratch is one slot per sequence, reused every step */
+    if (rc == CRGPU_OK) rc = grow(c, &c->d_ev, &c->d_ev_cap, (size_t)(B.ev_stride * na0));
+    if (rc == CRGPU_OK) rc = grow(c, &c->d_lens, &c->d_lens_cap, (size_t)(B.lens_stride * na0));
+    if (rc == CRGPU_OK) rc = grow(c, &c->d_done, &c->d_done_cap, (size_t)na0 + 16u);
+    if (rc == CRGPU_OK) rc = grow(c, &m->d_desc, &m->desc_cap, (size_t)nb * 28u);
+    if (rc != CRGPU_OK) { free(h); return rc; }
+    c->done_blocks = 0;
+    B.ev = c->d_ev; B.lens = c->d_lens; B.pre_done = c->d_done;
+    u64* const d_in_off = (u64*)m->d_desc, * const d_out_off = d_in_off + nb;
+    uint32_t* const d_in_size = (uint32_t*)(d_out_off + nb), * const d_osz = d_in_size + nb, * const d_map = d_osz + nb;
+    CrSeq Q;
+    Q.store = m->d_store; Q.log = m->d_log; Q.log_stride = m->log_stride; Q.off_log3 = m->off_log3;
+    Q.slot = m->d_idx; Q.chain_ctr = m->d_idx + 2u * (size_t)m->nseq;
+    e = hipMemcpyAsync(d_map, h_map, 4u * nb, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(m->d_idx, h_perm, 4u * nseq, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) { crs_launch_gather(c->stream, d_map, nb, (const u64*)in_off, in_size, (const u64*)out_off, d_in_off, d_in_size, d_out_off); e = hipGetLastError(); }
+    if (e != hipSuccess) rc = fail(c, e, "hipMemcpyAsync(sequence tables)");
+    const uint32_t grid_cap = A->wgs;
+    p = 0;
+    for (uint32_t t = 0; t < steps && rc == CRGPU_OK; t++) {
+        uint32_t na = 0;
+        while (na < nseq && seq_first[h_perm[na] + 1u] - seq_first[h_perm[na]] > t) na++;
+        B.in_off = d_in_off + p; B.in_size = d_in_size + p; B.out_off = d_out_off + p; B.out_size = d_osz + p; B.nblocks = na;
+        rc = seq_step(c, B, A->L, Q, h_perm, h_n + p, h_got, na < grid_cap ? na : grid_cap);
+        p += na;
+    }
+    if (rc == CRGPU_OK) {
+        crs_launch_scatter(c->stream, d_map, nb, d_osz, out_size);
+        e = hipGetLastError();
+        if (e != hipSuccess) rc = fail(c, e, "k_seq_scatter");
+    }
+    e = hipStreamSynchronize(c->stream);                                    /* (also: the host tables above are still being read) */
+    if (e != hipSuccess && rc == CRGPU_OK) rc = fail(c, e, "hipStreamSynchronize");
+    free(h);
+    return rc;
+}
+
 /* ------------------------------------------------------------------ static dictionary (device copy) */
 
 struct crgpu_dict {
@@ -1973,7 +2206,8 @@ static int grow(crgpu_ctx* c, uint8_t** p, size_t* cap, size_t want) {
 
 static int host_call(crgpu_ctx* c, int codec, crgpu_dict* dict, int decode, const uint8_t* in, const uint64_t* in_off,
                      const uint32_t* in_size, uint32_t nblocks, uint8_t* out, const uint64_t* out_off,
-                     const uint32_t* out_cap, uint32_t* out_size, crgpu_models* models = NULL) {
+                     const uint32_t* out_cap, uint32_t* out_size, crgpu_models* models = NULL,
+                     crgpu_model_set* set = NULL, const uint32_t* seq_first = NULL, uint32_t nseq = 0) {
     if (!c) return CRGPU_E_ARG;
     if (nblocks == 0) return CRGPU_OK;
     if (!in || !in_off || !in_size || !out || !out_off || !out_size || (decode && !out_cap)) return CRGPU_E_ARG;
@@ -2028,6 +2262,7 @@ static int host_call(crgpu_ctx* c, int codec, crgpu_dict* dict, int decode, cons
     else if (dict)      rc = crgpu_dict_encode_blocks_dev(c, dict, c->d_in, d_in_off, d_in_size, nblocks, max_block, c->d_out, d_out_off, d_out_size, 0);
     else if (decode)    rc = crgpu_decode_blocks_dev(c, codec, c->d_in, d_in_off, d_in_size, nblocks, max_block, c->d_out, d_out_off, d_cap, d_out_size, 0);
     else if (models)    rc = crgpu_encode_blocks_carried_dev(c, codec, models, c->d_in, d_in_off, d_in_size, nblocks, c->d_out, d_out_off, d_out_size);
+    else if (set)       rc = crgpu_encode_sequences_carried_dev(c, codec, set, c->d_in, d_in_off, d_in_size, seq_first, nseq, c->d_out, d_out_off, d_out_size);
     else                rc = crgpu_encode_blocks_dev(c, codec, c->d_in, d_in_off, d_in_size, nblocks, max_block, c->d_out, d_out_off, d_out_size, 0);
     if (rc == CRGPU_OK) {
         e = hipMemcpyAsync(out_size, d_out_size, 4u * nblocks, hipMemcpyDeviceToHost, c->stream);
@@ -2067,6 +2302,24 @@ extern "C" int crgpu_encode_blocks_carried(crgpu_ctx* c, int codec, crgpu_models
     if (!m) return CRGPU_E_ARG;
     if (c && codec != CRGPU_CODEC_ROP) { snprintf(c->err, sizeof c->err, "models are carried for comprop only (codec %d)", codec); return CRGPU_E_ARG; }
     return host_call(c, codec, NULL, 0, in, in_off, in_size, nblocks, out, out_off, NULL, out_size, m);
+}
+/* the blocks seq_first[0] .. seq_first[nseq] - 1 are packed on the device; the sequences' first blocks are counted from there */
+extern "C" int crgpu_encode_sequences_carried(crgpu_ctx* c, int codec, crgpu_model_set* m, const uint8_t* in, const uint64_t* in_off,
+                                              const uint32_t* in_size, const uint32_t* seq_first, uint32_t nseq,
+                                              uint8_t* out, const uint64_t* out_off, uint32_t* out_size) {
+    if (!c || !m || (nseq && !seq_first)) return CRGPU_E_ARG;
+    if (codec != CRGPU_CODEC_ROP) { snprintf(c->err, sizeof c->err, "models are carried for comprop only (codec %d)", codec); return CRGPU_E_ARG; }
+    for (uint32_t s = 0; s < nseq; s++) if (seq_first[s + 1u] < seq_first[s]) { snprintf(c->err, sizeof c->err, "seq_first descends at sequence %u", s); return CRGPU_E_ARG; }
+    if (nseq == 0) return crgpu_encode_sequences_carried_dev(c, codec, m, NULL, NULL, NULL, NULL, 0, NULL, NULL, NULL);   /* (its refusals hold for an empty call too) */
+    uint32_t* rel = (uint32_t*)malloc(sizeof(uint32_t) * ((size_t)nseq + 1u));
+    if (!rel) return CRGPU_E_NOMEM;
+    const uint32_t first = seq_first[0];
+    for (uint32_t s = 0; s <= nseq; s++) rel[s] = seq_first[s] - first;
+    const int rc = rel[nseq] == 0 ? crgpu_encode_sequences_carried_dev(c, codec, m, NULL, NULL, NULL, rel, nseq, NULL, NULL, NULL)
+                                  : host_call(c, codec, NULL, 0, in, in_off ? in_off + first : NULL, in_size ? in_size + first : NULL, rel[nseq], out,
+                                              out_off ? out_off + first : NULL, NULL, out_size ? out_size + first : NULL, NULL, m, rel, nseq);
+    free(rel);
+    return rc;
 }
 extern "C" int crgpu_decode_blocks(crgpu_ctx* c, int codec, const uint8_t* in, const uint64_t* in_off,
                                    const uint32_t* in_size, uint32_t nblocks, uint8_t* out,

@@ -51,9 +51,11 @@ void crc_launch_o2(hipStream_t s, uint32_t grid, const CrBatch& B1, uint8_t* M);
 void crc_launch_o1(hipStream_t s, const CrBatch& B1, uint8_t* M);
 void crc_launch_abort(hipStream_t s, const CrBatch& B1, uint8_t* M);
 
-#ifdef CRGPU_CARRY_TU
+/* CRGPU_CARRY_FUNCS: the chain walkers below without the kernels, for a translation unit with kernels of its own (crgpu_seq.h) */
+#if defined(CRGPU_CARRY_TU) || defined(CRGPU_CARRY_FUNCS)
 #include "crgpu_rop2.h"
 
+#ifdef CRGPU_CARRY_TU
 /* ppm_model_init: every order-1 count 1, no order-2 byte seen (flag counts 1 / 1), order-3 cells and the register 0 */
 __global__ __launch_bounds__(256) void k_ropc_fill(uint8_t* M) {
     const u64 words = CR_M_BYTES / 16u;
@@ -65,17 +67,20 @@ __global__ __launch_bounds__(256) void k_ropc_fill(uint8_t* M) {
         reinterpret_cast<uint4*>(M)[w] = v;
     }
 }
+#endif
 
 /* ------------------------------------------------------------------ order 3 */
 
 /* cr_rop_o3_chain with the table entry taken from and returned to the store. The chain's key comes from its first event's
  * context (order-3 slot -> order-2 slot -> event): three dependent loads, once per chain. A carried chain may predict a byte
  * at its first event already, so every prediction is stored, 0 included (the sorts cleared cpred in passing; storing a 0 over
- * it is only a request more) */
-CR_DEV void cr_ropc_o3_chain(CrEvViews& V, uint16_t* o3, uint32_t s) {
+ * it is only a request more). LOG (crgpu_seq.h): the chain's start state {key, old cell} goes to *log before the walk */
+template <bool LOG = false>
+CR_DEV void cr_ropc_o3_chain(CrEvViews& V, uint16_t* o3, uint32_t s, uint2* log = nullptr) {
     uint32_t n_sym = V.csym3[s], n_slot = V.cslot3[s];
     const uint32_t key = cr_o3_key(V.ev_ctx[V.list2[n_slot]]);
     const uint32_t cell = o3[key];
+    if constexpr (LOG) *log = make_uint2(key, cell);
     uint32_t pred = cell & 0xffu, conf = cell >> 8;
     for (;;) {
         const uint32_t sy = n_sym, slot = n_slot;
@@ -96,6 +101,7 @@ CR_DEV void cr_ropc_o3_chain(CrEvViews& V, uint16_t* o3, uint32_t s) {
     o3[key] = (uint16_t)(pred | (conf << 8));
 }
 
+#ifdef CRGPU_CARRY_TU
 __global__ __launch_bounds__(256) void k_ropc_o3(CrBatch B, uint8_t* M) {
     CrEvViews V = cr_ev_views(B.ev, B.ev_cap);
     const uint32_t nev = V.ctr[0];
@@ -106,6 +112,7 @@ __global__ __launch_bounds__(256) void k_ropc_o3(CrBatch B, uint8_t* M) {
     uint16_t* const o3 = reinterpret_cast<uint16_t*>(M + CR_M_OFF_O3);
     for (uint32_t c = gt; c < nc; c += gn) cr_ropc_o3_chain(V, o3, V.starts3[c]);
 }
+#endif
 
 /* ------------------------------------------------------------------ order 2 */
 
@@ -147,8 +154,11 @@ CR_DEV void cr_ln_save(const CrLaneNode& nd, uint8_t* rec) {
 
 /* cr_rop_o2_all with the chain's record around it. The record's address comes from the first event's context, fetched with
  * the chain's first operands; cr_rop_o2_event's shortcuts (an empty node stores no exclusion set, a triple equal to
- * CR_TRIP_FRESH is not stored) test the node itself, and the node is what the store says */
-CR_DEV void cr_ropc_o2_all(CrEvViews& V, uint8_t* lane_node, uint8_t* o2, uint32_t nchains, uint32_t* next_chain /* device memory */) {
+ * CR_TRIP_FRESH is not stored) test the node itself, and the node is what the store says. LOG (crgpu_seq.h): chain h writes
+ * its start state to the 280-byte record h of `log` — the record's 256 counts if it holds any, its flag word at 256, the
+ * context at 260 — in 8-byte pieces (280 is no multiple of 16) */
+template <bool LOG = false>
+CR_DEV void cr_ropc_o2_all(CrEvViews& V, uint8_t* lane_node, uint8_t* o2, uint32_t nchains, uint32_t* next_chain /* device memory */, uint8_t* log = nullptr) {
     CrLaneNode nd;
     nd.cnt = lane_node; nd.bytes = 0; nd.fh = 1; nd.fe = 1;
     uint32_t at = 0, end = 0;
@@ -163,6 +173,15 @@ CR_DEV void cr_ropc_o2_all(CrEvViews& V, uint8_t* lane_node, uint8_t* o2, uint32
             at = (uint32_t)ch; end = (uint32_t)(ch >> 32);
             n_i = V.list2[at]; n_sp = (uint32_t)V.csym2[at] | ((uint32_t)V.cpred[at] << 16);
             rec = o2 + (u64)(V.ev_ctx[n_i] & 0xffffu) * CR_M_O2_REC;
+            if constexpr (LOG) {
+                uint2* const lr = reinterpret_cast<uint2*>(log + (u64)h * 280u);
+                const uint32_t fl = *reinterpret_cast<const uint32_t*>(rec + 256u);
+                lr[32] = make_uint2(fl, V.ev_ctx[n_i] & 0xffffu);
+                if (fl >> 16) {
+#pragma unroll
+                    for (uint32_t q = 0; q < 32u; q++) lr[q] = reinterpret_cast<const uint2*>(rec)[q];
+                }
+            }
             cr_ln_load(nd, rec);
         }
         const uint32_t i = n_i, sp = n_sp;
@@ -172,6 +191,7 @@ CR_DEV void cr_ropc_o2_all(CrEvViews& V, uint8_t* lane_node, uint8_t* o2, uint32
     }
 }
 
+#ifdef CRGPU_CARRY_TU
 __global__ __launch_bounds__(CR_O2C_THREADS) void k_ropc_o2(CrBatch B, uint8_t* M) {
     __shared__ __attribute__((aligned(16))) uint8_t s_nodes[CR_O2C_THREADS * CR_LN_STRIDE];
     CrEvViews V = cr_ev_views(B.ev, B.ev_cap);
@@ -239,5 +259,6 @@ __global__ __launch_bounds__(CRGPU_WAVE) void k_ropc_abort(CrBatch B, uint8_t* M
     }
 }
 
-#endif /* CRGPU_CARRY_TU */
+#endif /* CRGPU_CARRY_TU: the kernels */
+#endif /* CRGPU_CARRY_TU || CRGPU_CARRY_FUNCS */
 #endif

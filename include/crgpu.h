@@ -137,6 +137,35 @@ int crgpu_encode_blocks_carried(crgpu_ctx* ctx, int codec, crgpu_models* m,
                                 const uint8_t* in, const uint64_t* in_off, const uint32_t* in_size, uint32_t nblocks,
                                 uint8_t* out, const uint64_t* out_off, uint32_t* out_size);
 
+/* Many sequences of dependent comprop blocks in one call (an archive's members, a directory, a request queue): step t of the
+ * call codes block t of every sequence that has one, in one pass of the kernel pipeline. A crgpu_model_set holds `nseq` model
+ * stores (slots, 26 280 192 bytes each) for blocks of up to `max_block` bytes, and per slot an undo log of
+ *   65 792 + 280 x min(E, 65 536) + 8 x min(E, 1 << 22) bytes, E = align_up(max(max_block, 1024) + max_block / 64 + 128, 64)
+ * — the chain start states a block overwrites, which a block that ends stored goes back to: no second store per sequence
+ * and no store-sized copy per block. create leaves every slot in the ppm_model_init state; reset puts the slots
+ * which[0 .. n) back there (which == NULL: all of them; `which` is HOST memory). The set belongs to its context. */
+typedef struct crgpu_model_set crgpu_model_set;
+int  crgpu_model_set_create(crgpu_ctx* ctx, uint32_t nseq, uint32_t max_block, crgpu_model_set** out);
+void crgpu_model_set_destroy(crgpu_model_set* set);
+int  crgpu_model_set_reset(crgpu_ctx* ctx, crgpu_model_set* set, const uint32_t* which, uint32_t n);
+/* Pointer conventions of crgpu_encode_blocks_dev, except seq_first: HOST memory, nseq + 1 entries, ascending. Sequence s owns
+ * the blocks seq_first[s] .. seq_first[s + 1] - 1 of the flat block arrays (it may own none) and slot s of the set: its first
+ * block starts from the slot's state, block i continues block i - 1, and on return the slot holds the state behind the
+ * sequence's last block — so a sequence may be fed in slices over several calls; a slot without a block in a call is not
+ * touched. Every block's bytes are what the reference's lzencode writes for it in its sequence; the rules of
+ * crgpu_encode_blocks_carried_dev for blocks under 16 bytes and blocks that end stored hold per sequence. CRGPU_E_ARG for a
+ * codec other than CRGPU_CODEC_ROP, a one-wave context, a block above the set's max_block, more sequences than slots, a
+ * descending seq_first and a set of another context. The call returns when all blocks are coded. */
+int crgpu_encode_sequences_carried_dev(crgpu_ctx* ctx, int codec, crgpu_model_set* set,
+                                       const uint8_t* in, const uint64_t* in_off, const uint32_t* in_size,
+                                       const uint32_t* seq_first, uint32_t nseq,
+                                       uint8_t* out, const uint64_t* out_off, uint32_t* out_size);
+/* ... and with HOST pointers (the conventions of crgpu_encode_blocks) */
+int crgpu_encode_sequences_carried(crgpu_ctx* ctx, int codec, crgpu_model_set* set,
+                                   const uint8_t* in, const uint64_t* in_off, const uint32_t* in_size,
+                                   const uint32_t* seq_first, uint32_t nseq,
+                                   uint8_t* out, const uint64_t* out_off, uint32_t* out_size);
+
 /* Device-side concatenation of a batch (`k_pack`; the write loop of src/main.c:198-205 as one contiguous run):
  * payload b = in[in_off[b] .. +in_size[b]) is copied to out[out_off[b] ..) where out_off is the exclusive sum of the
  * slots in front of it. with_headers != 0: every non-empty block is preceded by the container's packed
