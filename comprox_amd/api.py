@@ -115,6 +115,18 @@ def load_library():
     L.crgpu_encode_sequences_carried_dev.argtypes = [vp, i32, vp, vp, vp, vp, vp, u32, vp, vp, vp]
     L.crgpu_encode_sequences_carried.restype = i32
     L.crgpu_encode_sequences_carried.argtypes = [vp, i32, vp, vp, vp, vp, vp, u32, vp, vp, vp]
+    L.crgpu_decode_set_create.restype = i32
+    L.crgpu_decode_set_create.argtypes = [vp, u32, u32, ctypes.POINTER(vp)]
+    L.crgpu_decode_set_destroy.restype = None
+    L.crgpu_decode_set_destroy.argtypes = [vp]
+    L.crgpu_decode_set_reset.restype = i32
+    L.crgpu_decode_set_reset.argtypes = [vp, vp, vp, u32]
+    L.crgpu_decode_set_dense_nodes.restype = i32
+    L.crgpu_decode_set_dense_nodes.argtypes = [vp, vp, u32, ctypes.POINTER(u32)]
+    L.crgpu_decode_sequences_carried_dev.restype = i32
+    L.crgpu_decode_sequences_carried_dev.argtypes = [vp, i32, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, i32]
+    L.crgpu_decode_sequences_carried.restype = i32
+    L.crgpu_decode_sequences_carried.argtypes = [vp, i32, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
     L.crgpu_shim_pipeline_carry.restype = None
     L.crgpu_shim_pipeline_carry.argtypes = [i32]
     L.crgpu_dict_create.restype = i32
@@ -379,6 +391,45 @@ class CrGpu:
                                                                 len(seq_first) - 1, d_out, d_out_off, d_out_size),
                     "crgpu_encode_sequences_carried_dev")
 
+    def decode_set_create(self, nseq: int, max_block: int) -> "CrDecodeSet":
+        return CrDecodeSet(self, nseq, max_block)
+
+    def decode_sequences(self, sequences, caps, decode_set: "CrDecodeSet", strict: bool = True, codec: int = CODEC_ROP):
+        """sequences: list of lists of encoded blocks, sequence s on slot s of the set; caps: the room for every decoded block,
+        in the same shape. All sequences are decoded in one kernel launch, each block continuing the models of the one before
+        (the first one the slot's state). Returns the decoded bytes in the same shape, None for a block that failed (and for
+        every block behind it in its sequence); with strict a failed block raises."""
+        blocks = [b for seq in sequences for b in seq]
+        seq_first = np.zeros(len(sequences) + 1, dtype=np.uint32)
+        seq_first[1:] = np.cumsum([len(seq) for seq in sequences], dtype=np.uint64)
+        return self._decode_sequences_flat(blocks, [c for seq in caps for c in seq], seq_first, decode_set, strict, codec)
+
+    def _decode_sequences_flat(self, blocks, caps, seq_first, decode_set, strict=True, codec=CODEC_ROP):
+        nb = len(blocks)
+        sizes = np.array([len(b) for b in blocks] or [0], dtype=np.uint32)
+        in_off = np.zeros(len(sizes), dtype=np.uint64)
+        in_off[1:] = np.cumsum(sizes[:-1], dtype=np.uint64)
+        src = np.frombuffer(b"".join(bytes(b) for b in blocks) or b"\0", dtype=np.uint8)
+        caps = np.array(list(caps) or [0], dtype=np.uint32)
+        out_off = np.zeros(len(caps), dtype=np.uint64)
+        out_off[1:] = np.cumsum(caps[:-1].astype(np.uint64), dtype=np.uint64)
+        out = np.zeros(max(1, int(caps.astype(np.uint64).sum())), dtype=np.uint8)
+        out_size = np.zeros(len(sizes), dtype=np.uint32)
+        seq_first = np.ascontiguousarray(seq_first, dtype=np.uint32)
+        rc = self.lib.crgpu_decode_sequences_carried(self.h, codec, decode_set.h, _ptr(src), _ptr(in_off), _ptr(sizes), _ptr(seq_first),
+                                                     len(seq_first) - 1, _ptr(out), _ptr(out_off), _ptr(caps), _ptr(out_size))
+        self._check(rc, "crgpu_decode_sequences_carried", allow=() if strict else (-4,))
+        res = [None if int(s) == 0xFFFFFFFF else out[int(o):int(o) + int(s)].tobytes() for o, s in zip(out_off[:nb], out_size[:nb])]
+        return [res[int(a):int(b)] for a, b in zip(seq_first[:-1], seq_first[1:])]
+
+    def decode_sequences_carried_dev(self, decode_set, d_in, d_in_off, d_in_size, seq_first, d_out, d_out_off, d_out_cap, d_out_size,
+                                     sync=False, strict=True, codec=CODEC_ROP):
+        """The same with everything in device memory except seq_first (host: len(sequences) + 1 ints); only enqueued unless sync."""
+        seq_first = np.ascontiguousarray(seq_first, dtype=np.uint32)
+        return self._check(self.lib.crgpu_decode_sequences_carried_dev(self.h, codec, decode_set.h, d_in, d_in_off, d_in_size, _ptr(seq_first),
+                                                                       len(seq_first) - 1, d_out, d_out_off, d_out_cap, d_out_size, int(sync)),
+                           "crgpu_decode_sequences_carried_dev", allow=() if strict else (-4,))
+
     def decode_blocks_dev(self, codec, d_in, d_in_off, d_in_size, nblocks, max_block, d_out, d_out_off, d_out_cap,
                           d_out_size, sync=False):
         self._check(self.lib.crgpu_decode_blocks_dev(self.h, codec, d_in, d_in_off, d_in_size, nblocks, max_block,
@@ -594,6 +645,41 @@ class CrModelSet:
     def close(self):
         if self.h:
             self.gpu.lib.crgpu_model_set_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CrDecodeSet:
+    """`nseq` decoder models of comprop in the batched decoder's own format (crgpu_decode_set), one slot per sequence of dependent blocks."""
+
+    def __init__(self, gpu: CrGpu, nseq: int, max_block: int):
+        self.gpu = gpu
+        self.nseq = nseq
+        self.h = ctypes.c_void_p()
+        gpu._check(gpu.lib.crgpu_decode_set_create(gpu.h, nseq, max_block, ctypes.byref(self.h)), "crgpu_decode_set_create")
+
+    def reset(self, which=None):
+        """every slot, or the slots listed in `which`, back to the state of reset_models() (and no longer poisoned)"""
+        w = None if which is None else np.array(list(which), dtype=np.uint32)
+        if w is not None and len(w) == 0:
+            return
+        self.gpu._check(self.gpu.lib.crgpu_decode_set_reset(self.gpu.h, self.h, None if w is None else _ptr(w), 0 if w is None else len(w)),
+                        "crgpu_decode_set_reset")
+
+    def dense_nodes(self, slot: int) -> int:
+        """diagnostic: order-2 nodes of the slot that have outgrown their line"""
+        n = ctypes.c_uint32()
+        self.gpu._check(self.gpu.lib.crgpu_decode_set_dense_nodes(self.gpu.h, self.h, slot, ctypes.byref(n)), "crgpu_decode_set_dense_nodes")
+        return int(n.value)
+
+    def close(self):
+        if self.h:
+            self.gpu.lib.crgpu_decode_set_destroy(self.h)
             self.h = ctypes.c_void_p()
 
     def __del__(self):

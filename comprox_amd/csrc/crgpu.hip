@@ -29,6 +29,7 @@
 #include "crgpu_links2.h"
 #include "crgpu_carry.h"
 #include "crgpu_seq.h"
+#include "crgpu_seqdec.h"
 #include "crgpu_rolz3.h"
 #include "crgpu_rox3.h"
 #include "crgpu_dicpick.h"
@@ -1042,7 +1043,7 @@ static uint32_t pow2_at_least(u64 want, uint32_t lo, uint32_t hi) {
 #define CR_USE_DMODEL 2048u     /* the batched decoders' model tables: directory, node lines, order-1 rows, direct order-3 table, dense slots */
 enum { CR_AR_ENC = 0, CR_AR_DEC = 1, CR_AR_ALL = 2 };
 
-static CrArenaLayout make_layout(uint32_t max_block, uint32_t use) {
+static CrArenaLayout make_layout(uint32_t max_block, uint32_t use, uint32_t dense_slots = 0) {
     CrArenaLayout L;
     memset(&L, 0, sizeof L);
     L.max_block = max_block;
@@ -1061,7 +1062,7 @@ static CrArenaLayout make_layout(uint32_t max_block, uint32_t use) {
     /* a node leaves its line with its 63rd symbol, every symbol of a node costs one coded escape, and a block of n bytes is
      * at most 2 n coding steps (an escape byte + a length symbol per token, damaged streams included): at most 2 n / 63
      * nodes of a block ever do */
-    L.dense_slots = 2u * (max_block / (CRGPU_LINE_PAIRS + 1u)) + 4u;
+    L.dense_slots = dense_slots ? dense_slots : 2u * (max_block / (CRGPU_LINE_PAIRS + 1u)) + 4u;   /* (dense_slots: a decode set's, whose nodes outlive the block) */
     CR_REGION(off_dense, CR_USE_DMODEL, (u64)L.dense_slots * CRGPU_NODE_BYTES);
     CR_REGION(off_o3, CR_USE_O3HASH, (u64)L.cap_o3 * 8u);
     CR_REGION(off_lz8, CR_USE_LZP, (u64)L.cap_lz * 8u);
@@ -1961,6 +1962,141 @@ extern "C" int crgpu_encode_sequences_carried_dev(crgpu_ctx* c, int codec, crgpu
     return rc;
 }
 
+/* ------------------------------------------------------------------ many sequences decoded in one launch (crgpu_seqdec.h) */
+
+struct crgpu_decode_set {
+    crgpu_ctx*    ctx;
+    uint32_t      nseq, max_block;
+    CrArenaLayout L;           /* of one slot; L.max_block is the set's own (the tables are sized for it rounded up to 1 KiB) */
+    uint8_t*      d_store;     /* nseq x L.stride */
+    uint32_t*     d_idx;       /* 3 x nseq + 1 words: a call's seq_first, its order, a reset's list */
+    uint32_t*     h_idx;       /* the same in pinned host memory: what a call uploads stays put until the call has run */
+};
+
+extern "C" int crgpu_decode_set_reset(crgpu_ctx* c, crgpu_decode_set* m, const uint32_t* which, uint32_t n) {
+    if (!c || !m || m->ctx != c) return CRGPU_E_ARG;
+    CR_TRY(c, hipSetDevice(c->device));
+    if (!which) {
+        crsd_launch_mark(c->stream, m->d_store, m->L.stride, NULL, m->nseq);
+        CR_TRY(c, hipGetLastError());
+        return CRGPU_OK;
+    }
+    if (n == 0) return CRGPU_OK;
+    if (n > m->nseq) { snprintf(c->err, sizeof c->err, "%u slots to reset, the set has %u", n, m->nseq); return CRGPU_E_ARG; }
+    for (uint32_t i = 0; i < n; i++) if (which[i] >= m->nseq) { snprintf(c->err, sizeof c->err, "slot %u of a set of %u", which[i], m->nseq); return CRGPU_E_ARG; }
+    CR_TRY(c, hipStreamSynchronize(c->stream));          /* (the pinned list of the reset before this one has been read) */
+    uint32_t* const h_list = m->h_idx + 2u * (size_t)m->nseq + 1u, * const d_list = m->d_idx + 2u * (size_t)m->nseq + 1u;
+    memcpy(h_list, which, 4u * (size_t)n);
+    CR_TRY(c, hipMemcpyAsync(d_list, h_list, 4u * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    crsd_launch_mark(c->stream, m->d_store, m->L.stride, d_list, n);
+    CR_TRY(c, hipGetLastError());
+    return CRGPU_OK;
+}
+
+extern "C" void crgpu_decode_set_destroy(crgpu_decode_set* m) {
+    if (!m) return;
+    (void)hipSetDevice(m->ctx->device);
+    (void)hipStreamSynchronize(m->ctx->stream);
+    (void)hipFree(m->d_store); (void)hipFree(m->d_idx);
+    if (m->h_idx) (void)hipHostFree(m->h_idx);
+    free(m);
+}
+
+extern "C" int crgpu_decode_set_create(crgpu_ctx* c, uint32_t nseq, uint32_t max_block, crgpu_decode_set** out) {
+    if (!c || !out) return CRGPU_E_ARG;
+    *out = NULL;
+    if (nseq == 0 || nseq > 65535u || max_block > CRGPU_MAX_BLOCK + 1u) { snprintf(c->err, sizeof c->err, "a decode set has 1 .. 65535 slots for blocks of up to CRGPU_MAX_BLOCK + 1 bytes"); return CRGPU_E_ARG; }
+    const CrArenaLayout L = make_layout((uint32_t)align_up(max_block < 1024u ? 1024u : max_block, 1024u), CR_USE_DMODEL | CR_USE_LZP | CR_USE_LZ2, CR_SD_DENSE_SLOTS);
+    if (L.stride == 0) { snprintf(c->err, sizeof c->err, "the decoder's layout cannot address the tables of %u-byte blocks", max_block); return CRGPU_E_ARG; }
+    CR_TRY(c, hipSetDevice(c->device));
+    crgpu_decode_set* m = (crgpu_decode_set*)calloc(1, sizeof *m);
+    if (!m) return CRGPU_E_NOMEM;
+    m->ctx = c; m->nseq = nseq; m->max_block = max_block; m->L = L; m->L.max_block = max_block;
+    const size_t words = 3u * (size_t)nseq + 1u;
+    if (hipMalloc((void**)&m->d_store, (size_t)(nseq * L.stride)) != hipSuccess || hipMalloc((void**)&m->d_idx, words * 4u) != hipSuccess ||
+        hipHostMalloc((void**)&m->h_idx, words * 4u, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        snprintf(c->err, sizeof c->err, "hipMalloc(decode set, %u x %llu bytes) failed", nseq, (unsigned long long)L.stride);
+        crgpu_decode_set_destroy(m);
+        return CRGPU_E_NOMEM;
+    }
+    /* all zero: generation words 0, every node tag and order-3 entry stale; the first pick-up of a slot does the rest */
+    hipError_t e = hipMemsetAsync(m->d_store, 0, (size_t)(nseq * L.stride), c->stream);
+    const int rc = e != hipSuccess ? fail(c, e, "hipMemsetAsync(decode set)") : crgpu_decode_set_reset(c, m, NULL, 0);
+    if (rc != CRGPU_OK) { crgpu_decode_set_destroy(m); return rc; }
+    *out = m;
+    return CRGPU_OK;
+}
+
+/* diagnostic: how many order-2 nodes of slot `slot` live in the dense area (the step's counter); waits for the stream */
+extern "C" int crgpu_decode_set_dense_nodes(crgpu_ctx* c, crgpu_decode_set* m, uint32_t slot, uint32_t* count) {
+    if (!c || !m || m->ctx != c || slot >= m->nseq || !count) return CRGPU_E_ARG;
+    CR_TRY(c, hipSetDevice(c->device));
+    CR_TRY(c, hipMemcpyAsync(count, m->d_store + (u64)slot * m->L.stride + CRGPU_OFF_SCRATCH + 904u, 4u, hipMemcpyDeviceToHost, c->stream));
+    CR_TRY(c, hipStreamSynchronize(c->stream));
+    return CRGPU_OK;
+}
+
+/* Sequence s owns blocks seq_first[s] .. seq_first[s + 1] - 1 (seq_first in HOST memory, everything else on the device) and
+ * slot s of the set. The block sizes come back to the host once, in front of the launch: the refusal of an oversized block
+ * and the order of the sequences — most coded bytes first, so the longest chain starts first and the launch ends with it —
+ * need them. Then ONE launch, no host wait inside; with sync == 0 the call returns when it is enqueued. */
+extern "C" int crgpu_decode_sequences_carried_dev(crgpu_ctx* c, int codec, crgpu_decode_set* m, const uint8_t* in, const uint64_t* in_off,
+                                                  const uint32_t* in_size, const uint32_t* seq_first, uint32_t nseq,
+                                                  uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_size, int sync) {
+    if (!c || !m || m->ctx != c || (nseq && !seq_first)) return CRGPU_E_ARG;
+    if (codec != CRGPU_CODEC_ROP) { snprintf(c->err, sizeof c->err, "models are carried for comprop only (codec %d)", codec); return CRGPU_E_ARG; }
+    if (nseq > m->nseq) { snprintf(c->err, sizeof c->err, "%u sequences for a set of %u slots", nseq, m->nseq); return CRGPU_E_ARG; }
+    for (uint32_t s = 0; s < nseq; s++) if (seq_first[s + 1u] < seq_first[s]) { snprintf(c->err, sizeof c->err, "seq_first descends at sequence %u", s); return CRGPU_E_ARG; }
+    const uint32_t first = nseq ? seq_first[0] : 0u, nb = nseq ? seq_first[nseq] - first : 0u;
+    if (nb == 0) return CRGPU_OK;
+    if (!in || !in_off || !in_size || !out || !out_off || !out_cap || !out_size) return CRGPU_E_ARG;
+    CR_TRY(c, hipSetDevice(c->device));
+    uint8_t* const h = (uint8_t*)malloc((size_t)nb * 4u + (size_t)nseq * 8u);
+    if (!h) return CRGPU_E_NOMEM;
+    u64* const h_sum = (u64*)h;
+    uint32_t* const h_size = (uint32_t*)(h_sum + nseq);
+    hipError_t e = hipMemcpyAsync(h_size, in_size + first, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);            /* (also: the set's pinned tables are free again) */
+    if (e != hipSuccess) { free(h); return fail(c, e, "hipMemcpyAsync(block sizes)"); }
+    const uint32_t room = crgpu_bound(CRGPU_CODEC_ROP, m->max_block);
+    for (uint32_t b = 0; b < nb; b++) if (h_size[b] > room) {
+        snprintf(c->err, sizeof c->err, "coded block of %u bytes, a block of the set's %u bytes codes to %u at most", h_size[b], m->max_block, room);
+        free(h); return CRGPU_E_ARG;
+    }
+    uint32_t* const h_first = m->h_idx, * const h_order = m->h_idx + nseq + 1u;
+    uint32_t na = 0;
+    for (uint32_t s = 0; s < nseq; s++) {
+        h_first[s] = seq_first[s];
+        h_sum[s] = 0;
+        for (uint32_t b = seq_first[s]; b < seq_first[s + 1u]; b++) h_sum[s] += h_size[b - first];
+        if (seq_first[s + 1u] > seq_first[s]) h_order[na++] = s;
+    }
+    h_first[nseq] = seq_first[nseq];
+    std::stable_sort(h_order, h_order + na, [h_sum](uint32_t a, uint32_t b) { return h_sum[a] > h_sum[b]; });
+    free(h);
+    CrSeqDec D;
+    D.in = in; D.in_off = (const u64*)in_off; D.in_size = in_size;
+    D.out = out; D.out_off = (const u64*)out_off; D.out_cap = out_cap; D.out_size = out_size;
+    D.seq_first = m->d_idx; D.order = m->d_idx + nseq + 1u; D.nactive = na;
+    D.ticket = c->ticket; D.store = m->d_store;
+    CR_TRY(c, hipMemcpyAsync(m->d_idx, m->h_idx, 4u * (2u * (size_t)nseq + 1u), hipMemcpyHostToDevice, c->stream));
+    CR_TRY(c, hipMemsetAsync(c->ticket, 0, 64, c->stream));
+    const uint32_t grid = na;
+    CR_CARRY_RC(carry_group_open(c));
+    CR_TRY(c, hipEventRecord(c->ev0, c->stream));
+    CR_CARRY_STAGE("k_seqdec_v5", crsd_launch_decode(c->stream, cr_resident_grid(c, crsd_decode_kernel(), CRGPU_WAVE, 0, grid), D, m->L));
+    CR_CARRY_RC(carry_group_close(c));
+    CR_TRY(c, hipEventRecord(c->ev1, c->stream));
+    c->timed = 1;
+    if (!sync) return CRGPU_OK;
+    uint32_t failed = 0;
+    CR_TRY(c, hipMemcpyAsync(&failed, c->ticket + 1, 4u, hipMemcpyDeviceToHost, c->stream));
+    CR_TRY(c, hipStreamSynchronize(c->stream));
+    if (failed) { snprintf(c->err, sizeof c->err, "%u blocks could not be decoded (out_size 0xFFFFFFFF)", failed); return CRGPU_E_CORRUPT; }
+    return CRGPU_OK;
+}
+
 /* ------------------------------------------------------------------ static dictionary (device copy) */
 
 struct crgpu_dict {
@@ -2207,7 +2343,7 @@ static int grow(crgpu_ctx* c, uint8_t** p, size_t* cap, size_t want) {
 static int host_call(crgpu_ctx* c, int codec, crgpu_dict* dict, int decode, const uint8_t* in, const uint64_t* in_off,
                      const uint32_t* in_size, uint32_t nblocks, uint8_t* out, const uint64_t* out_off,
                      const uint32_t* out_cap, uint32_t* out_size, crgpu_models* models = NULL,
-                     crgpu_model_set* set = NULL, const uint32_t* seq_first = NULL, uint32_t nseq = 0) {
+                     crgpu_model_set* set = NULL, const uint32_t* seq_first = NULL, uint32_t nseq = 0, crgpu_decode_set* dset = NULL) {
     if (!c) return CRGPU_E_ARG;
     if (nblocks == 0) return CRGPU_OK;
     if (!in || !in_off || !in_size || !out || !out_off || !out_size || (decode && !out_cap)) return CRGPU_E_ARG;
@@ -2260,6 +2396,7 @@ static int host_call(crgpu_ctx* c, int codec, crgpu_dict* dict, int decode, cons
     if (e != hipSuccess) { free(h_in_off); free(h_cap); return fail(c, e, "hipMemcpyAsync(H2D)"); }
     if (dict && decode) rc = crgpu_dict_decode_blocks_dev(c, dict, c->d_in, d_in_off, d_in_size, nblocks, max_block, c->d_out, d_out_off, d_cap, d_out_size, 0);
     else if (dict)      rc = crgpu_dict_encode_blocks_dev(c, dict, c->d_in, d_in_off, d_in_size, nblocks, max_block, c->d_out, d_out_off, d_out_size, 0);
+    else if (dset)      rc = crgpu_decode_sequences_carried_dev(c, codec, dset, c->d_in, d_in_off, d_in_size, seq_first, nseq, c->d_out, d_out_off, d_cap, d_out_size, 0);
     else if (decode)    rc = crgpu_decode_blocks_dev(c, codec, c->d_in, d_in_off, d_in_size, nblocks, max_block, c->d_out, d_out_off, d_cap, d_out_size, 0);
     else if (models)    rc = crgpu_encode_blocks_carried_dev(c, codec, models, c->d_in, d_in_off, d_in_size, nblocks, c->d_out, d_out_off, d_out_size);
     else if (set)       rc = crgpu_encode_sequences_carried_dev(c, codec, set, c->d_in, d_in_off, d_in_size, seq_first, nseq, c->d_out, d_out_off, d_out_size);
@@ -2318,6 +2455,25 @@ extern "C" int crgpu_encode_sequences_carried(crgpu_ctx* c, int codec, crgpu_mod
     const int rc = rel[nseq] == 0 ? crgpu_encode_sequences_carried_dev(c, codec, m, NULL, NULL, NULL, rel, nseq, NULL, NULL, NULL)
                                   : host_call(c, codec, NULL, 0, in, in_off ? in_off + first : NULL, in_size ? in_size + first : NULL, rel[nseq], out,
                                               out_off ? out_off + first : NULL, NULL, out_size ? out_size + first : NULL, NULL, m, rel, nseq);
+    free(rel);
+    return rc;
+}
+/* the decode twin: the same packing, every block's room from out_cap */
+extern "C" int crgpu_decode_sequences_carried(crgpu_ctx* c, int codec, crgpu_decode_set* m, const uint8_t* in, const uint64_t* in_off,
+                                              const uint32_t* in_size, const uint32_t* seq_first, uint32_t nseq,
+                                              uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_size) {
+    if (!c || !m || (nseq && !seq_first)) return CRGPU_E_ARG;
+    if (codec != CRGPU_CODEC_ROP) { snprintf(c->err, sizeof c->err, "models are carried for comprop only (codec %d)", codec); return CRGPU_E_ARG; }
+    for (uint32_t s = 0; s < nseq; s++) if (seq_first[s + 1u] < seq_first[s]) { snprintf(c->err, sizeof c->err, "seq_first descends at sequence %u", s); return CRGPU_E_ARG; }
+    if (nseq == 0) return crgpu_decode_sequences_carried_dev(c, codec, m, NULL, NULL, NULL, NULL, 0, NULL, NULL, NULL, NULL, 0);
+    uint32_t* rel = (uint32_t*)malloc(sizeof(uint32_t) * ((size_t)nseq + 1u));
+    if (!rel) return CRGPU_E_NOMEM;
+    const uint32_t first = seq_first[0];
+    for (uint32_t s = 0; s <= nseq; s++) rel[s] = seq_first[s] - first;
+    const int rc = rel[nseq] == 0 ? crgpu_decode_sequences_carried_dev(c, codec, m, NULL, NULL, NULL, rel, nseq, NULL, NULL, NULL, NULL, 0)
+                                  : host_call(c, codec, NULL, 1, in, in_off ? in_off + first : NULL, in_size ? in_size + first : NULL, rel[nseq], out,
+                                              out_off ? out_off + first : NULL, out_cap ? out_cap + first : NULL, out_size ? out_size + first : NULL,
+                                              NULL, NULL, rel, nseq, m);
     free(rel);
     return rc;
 }

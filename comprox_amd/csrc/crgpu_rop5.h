@@ -2172,9 +2172,14 @@ CR_DEV void cr_rop_decode_helper(uint32_t mb_at) {
                    "v45", "v46", "v47", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "vcc", "scc", "memory");
 }
 
-template <int HELPER, int DL>
+/* CARRY (crgpu_seqdec.h): the block continues the models its predecessor left in the arena instead of resetting them. The caller
+ * hands in what the prologue otherwise sets up — the two generations, the context register, the capacity of the dense area —
+ * and gets the register back; the dense-slot counter in the scratch line is left standing. A stored block touches neither. */
+struct CrV5Carry { uint32_t ctx, gen, g3, dslots; };
+
+template <int HELPER, int DL, int CARRY = 0>
 CR_DEV uint32_t cr_rop_decode_v5(const uint8_t* src_, uint32_t n, uint8_t* dst_, uint32_t cap, uint8_t* arena_,
-                                 const CrArenaLayout& L, uint32_t lds_scratch, u64* st) {
+                                 const CrArenaLayout& L, uint32_t lds_scratch, u64* st, CrV5Carry* carry = nullptr) {
     const uint8_t* const src = cr_uni_ptr(src_);
     uint8_t* const dst = cr_uni_ptr(dst_);
     uint8_t* const arena = cr_uni_ptr(arena_);
@@ -2196,14 +2201,17 @@ CR_DEV uint32_t cr_rop_decode_v5(const uint8_t* src_, uint32_t n, uint8_t* dst_,
     CrLzp z;
     cr_lzp_attach(z, arena, L, cr_log2_ceil_pow2(2u * total, 1024u, L.cap_lz));
     cr_lzp_reset(z);
-    uint32_t g3_;
-    const uint32_t gen = cr_uni(cr_v3_reset(arena, L, g3_));
+    uint32_t g3_, gen_;
+    if constexpr (CARRY) { gen_ = carry->gen; g3_ = carry->g3; }
+    else gen_ = cr_v3_reset(arena, L, g3_);
+    const uint32_t gen = cr_uni(gen_);
     const uint32_t g3 = cr_uni(g3_);
     /* where the dense slots start, the LDS address of the wave's 256 scratch bytes, the next free dense slot: the statement
      * reads them from the arena's scratch line (and writes the slot counter back there when it is left) */
     if (lane == 0) {
         uint32_t* scr = reinterpret_cast<uint32_t*>(arena + CRGPU_OFF_SCRATCH + 896u);
-        scr[0] = (uint32_t)L.off_dense; scr[1] = lds_scratch; scr[2] = 0u;
+        scr[0] = (uint32_t)L.off_dense; scr[1] = lds_scratch;
+        if constexpr (!CARRY) scr[2] = 0u;
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     cr_wave_sync();
@@ -2217,12 +2225,13 @@ CR_DEV uint32_t cr_rop_decode_v5(const uint8_t* src_, uint32_t n, uint8_t* dst_,
     uint32_t cache = cr_lane_get(win, 0), range = 0xFFFFFFFFu;
     uint32_t ib_hi = cr_lane_get(win, 1), ib_lo = cr_lane_get(win, 2), ibits = 64, widx = 3;
     uint32_t ctx = 0, have = CR_LZP_SKIP, learned = CR_LZP_SKIP, after_esc = 0;
+    if constexpr (CARRY) ctx = cr_uni(carry->ctx);
     u64 x8 = *reinterpret_cast<const cr_u64u*>(src + 10);                 /* the 8 bytes in front of the write position */
     uint32_t x8_lo = cr_uni((uint32_t)x8), x8_hi = cr_uni((uint32_t)(x8 >> 32));
     uint32_t pend_lo = 0, pend_hi = 0;                                   /* lane j: those 8 bytes for position learned + j */
     const uint32_t off8 = cr_uni((uint32_t)L.off_lz8), off4 = cr_uni((uint32_t)L.off_lz4), off2 = cr_uni((uint32_t)L.off_lz2);
     const uint32_t lzsh = cr_uni(z.shift);
-    const uint32_t dslots = cr_uni(L.dense_slots);
+    const uint32_t dslots = cr_uni(CARRY ? carry->dslots : L.dense_slots);
     cr_stamp(st, 4);
     if (st && lane == 0)                                                 /* tools/dec_blocks.py: where the wave runs (HW_ID | XCC_ID << 32) */
         st[6] = (u64)(uint32_t)__builtin_amdgcn_s_getreg(63492) | ((u64)(uint32_t)__builtin_amdgcn_s_getreg(63508) << 32);
@@ -2335,6 +2344,7 @@ CR_DEV uint32_t cr_rop_decode_v5(const uint8_t* src_, uint32_t n, uint8_t* dst_,
     if (st && lane == 0) { st[8] = __builtin_amdgcn_s_memtime() - pf_t0; st[9] = pf_wait; st[10] = 0; st[11] = pf_calls; st[12] = pf_steps; st[13] = 0; }
 #endif
     cr_stamp(st, 5);
+    if constexpr (CARRY) carry->ctx = ctx;
     return have;
 }
 

@@ -166,6 +166,45 @@ int crgpu_encode_sequences_carried(crgpu_ctx* ctx, int codec, crgpu_model_set* s
                                    const uint32_t* seq_first, uint32_t nseq,
                                    uint8_t* out, const uint64_t* out_off, uint32_t* out_size);
 
+/* ... and back: many sequences of dependent comprop blocks DECODED in one kernel launch. One wavefront takes a sequence and
+ * walks its blocks front to back, so S sequences decode side by side where the lzdecode shim decodes one block per call. A
+ * crgpu_decode_set holds `nseq` slots in one allocation; a slot is a decoder model in the batched decoder's own format —
+ * directory words, 65 536 node lines of 128 bytes, order-1 rows, the direct order-3 table u16[1 << 22], a dense area of
+ * 65 536 slots of 256 bytes (one per 16-bit context: a sequence of any length cannot run out) — and, PER SLOT, the LZP tables
+ * for blocks of up to `max_block` bytes, emptied in front of every block as matcher_init does. Bytes per slot:
+ *   34 144 256 + 16 x C,  C = the power of two at or above 2 x max(1024, max_block rounded up to 1 KiB), at most 1 << 26
+ * (36 241 408 for 64 KiB blocks). create leaves every slot in the ppm_model_init state; reset puts the slots which[0 .. n)
+ * back there (which == NULL: all of them; `which` is HOST memory) by marking them — the kernel that next picks a marked slot
+ * up does the work. CRGPU_E_ARG for no slot or more than 65 535, and for a max_block the decoder's layout cannot address
+ * (above CRGPU_MAX_BLOCK + 1); CRGPU_E_NOMEM when the allocation fails. The set belongs to its context. */
+typedef struct crgpu_decode_set crgpu_decode_set;
+int  crgpu_decode_set_create(crgpu_ctx* ctx, uint32_t nseq, uint32_t max_block, crgpu_decode_set** out);
+void crgpu_decode_set_destroy(crgpu_decode_set* set);
+int  crgpu_decode_set_reset(crgpu_ctx* ctx, crgpu_decode_set* set, const uint32_t* which, uint32_t n);
+/* diagnostic: the order-2 nodes of a slot that have outgrown their line and live in its dense area; waits for the stream */
+int  crgpu_decode_set_dense_nodes(crgpu_ctx* ctx, crgpu_decode_set* set, uint32_t slot, uint32_t* count);
+/* Pointer conventions of crgpu_decode_blocks_dev, except seq_first: HOST memory, nseq + 1 entries, ascending. Sequence s owns
+ * the blocks seq_first[s] .. seq_first[s + 1] - 1 and slot s: block 0 starts from the slot's state, block i continues block
+ * i - 1, and on return the slot holds the state behind the sequence's last block — so a sequence may be fed in slices over
+ * several calls; a slot without a block in a call is not touched. Every block's output is what the reference's lzdecode
+ * produces for it in that sequence; a stored block is copied out and leaves the models and the context register alone.
+ * A block fails — out_size = 0xFFFFFFFF — on a header shorter than 20 bytes, an original size above out_cap or above the
+ * set's max_block, or a damaged stream; every later block of its slot then reports 0xFFFFFFFF undecoded, in this call and in
+ * later ones, until the slot is reset. CRGPU_E_ARG for a codec other than CRGPU_CODEC_ROP, more sequences than slots, a
+ * descending seq_first, a set of another context and a block whose in_size exceeds crgpu_bound(CRGPU_CODEC_ROP, max_block).
+ * The block sizes are read back once in front of the launch (that check and the order of the sequences need them); the
+ * decode itself is one launch that the call only enqueues unless `sync` is non-zero, in which case it returns
+ * CRGPU_E_CORRUPT if a block failed, after every other sequence has been decoded. */
+int crgpu_decode_sequences_carried_dev(crgpu_ctx* ctx, int codec, crgpu_decode_set* set,
+                                       const uint8_t* in, const uint64_t* in_off, const uint32_t* in_size,
+                                       const uint32_t* seq_first, uint32_t nseq,
+                                       uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_size, int sync);
+/* ... and with HOST pointers (the conventions of crgpu_decode_blocks; CRGPU_E_CORRUPT as there) */
+int crgpu_decode_sequences_carried(crgpu_ctx* ctx, int codec, crgpu_decode_set* set,
+                                   const uint8_t* in, const uint64_t* in_off, const uint32_t* in_size,
+                                   const uint32_t* seq_first, uint32_t nseq,
+                                   uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_size);
+
 /* Device-side concatenation of a batch (`k_pack`; the write loop of src/main.c:198-205 as one contiguous run):
  * payload b = in[in_off[b] .. +in_size[b]) is copied to out[out_off[b] ..) where out_off is the exclusive sum of the
  * slots in front of it. with_headers != 0: every non-empty block is preceded by the container's packed
