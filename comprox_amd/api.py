@@ -23,6 +23,7 @@ OPT_STAGE_LOG = 7
 OPT_DECODER_HELPER = 8
 OPT_DECODER_LDS_NODES = 9
 OPT_DICPICK_EPOCHS = 10
+OPT_SEQDEC_GRID = 11
 _HEADER = {CODEC_ROP: 20, CODEC_ROX: 32, CODEC_ROLZ: 16}
 
 _LIB = None

@@ -963,6 +963,7 @@ struct crgpu_ctx {
     int         one_wave_encoder;   /* CRGPU_OPT_ONE_WAVE_ENCODER: the model-carrying one-wave coders instead of the kernel pipeline */
     int         one_wave_decoder;   /* CRGPU_OPT_ONE_WAVE_DECODER: the model-carrying C++ decoders instead of the assembly step */
     uint32_t    lzp_grid, match_grid;   /* experiments: at most this many workgroups for the pre-pass kernels (0 = no limit) */
+    uint32_t    seqdec_grid;            /* the same for k_seqdec_v5: its waves then walk several sequences in one launch */
     int         decoder_helper;     /* CRGPU_OPT_DECODER_HELPER: comprop's batched decoder with a helper wave per block (k_rop_decode_v5h) */
     int         decoder_small_lds;  /* CRGPU_OPT_DECODER_LDS_NODES 0: k_rop_decode_v5s, no dense nodes in LDS */
     struct { const void* k; uint32_t dyn; int per_cu; } occ[48];   /* cr_resident_grid: workgroups per CU the runtime reports, per kernel */
@@ -1135,6 +1136,7 @@ extern "C" int crgpu_create(crgpu_ctx** out, int device) {
     static const struct { const char* env; int opt; } k_env[] = {
         {"CRGPU_WG_PER_CU", CRGPU_OPT_WG_PER_CU}, {"CRGPU_ONE_WAVE_ENCODER", CRGPU_OPT_ONE_WAVE_ENCODER},
         {"CRGPU_ONE_WAVE_DECODER", CRGPU_OPT_ONE_WAVE_DECODER}, {"CRGPU_LZP_GRID", CRGPU_OPT_LZP_GRID}, {"CRGPU_MATCH_GRID", CRGPU_OPT_MATCH_GRID},
+        {"CRGPU_SEQDEC_GRID", CRGPU_OPT_SEQDEC_GRID},
         {"CRGPU_LZP_TABLES", CRGPU_OPT_LZP_TABLES}, {"CRGPU_DECODER_HELPER", CRGPU_OPT_DECODER_HELPER},
         {"CRGPU_DECODER_LDS_NODES", CRGPU_OPT_DECODER_LDS_NODES}};
     for (size_t i = 0; i < sizeof k_env / sizeof k_env[0]; i++) {
@@ -1153,6 +1155,7 @@ extern "C" int crgpu_set_option(crgpu_ctx* c, int option, int value) {
         case CRGPU_OPT_ONE_WAVE_DECODER: c->one_wave_decoder = value != 0; return CRGPU_OK;
         case CRGPU_OPT_LZP_GRID:         c->lzp_grid = (uint32_t)value; return CRGPU_OK;
         case CRGPU_OPT_MATCH_GRID:       c->match_grid = (uint32_t)value; return CRGPU_OK;
+        case CRGPU_OPT_SEQDEC_GRID:      c->seqdec_grid = (uint32_t)value; return CRGPU_OK;
         case CRGPU_OPT_LZP_TABLES:       c->lzp_tables_only = value != 0; return CRGPU_OK;
         case CRGPU_OPT_DECODER_HELPER:   c->decoder_helper = value != 0; return CRGPU_OK;
         case CRGPU_OPT_DECODER_LDS_NODES: c->decoder_small_lds = value == 0; return CRGPU_OK;
@@ -2082,7 +2085,7 @@ extern "C" int crgpu_decode_sequences_carried_dev(crgpu_ctx* c, int codec, crgpu
     D.ticket = c->ticket; D.store = m->d_store;
     CR_TRY(c, hipMemcpyAsync(m->d_idx, m->h_idx, 4u * (2u * (size_t)nseq + 1u), hipMemcpyHostToDevice, c->stream));
     CR_TRY(c, hipMemsetAsync(c->ticket, 0, 64, c->stream));
-    const uint32_t grid = na;
+    const uint32_t grid = c->seqdec_grid && c->seqdec_grid < na ? c->seqdec_grid : na;   /* experiment and tests: fewer workgroups than sequences, so a wave takes a second ticket */
     CR_CARRY_RC(carry_group_open(c));
     CR_TRY(c, hipEventRecord(c->ev0, c->stream));
     CR_CARRY_STAGE("k_seqdec_v5", crsd_launch_decode(c->stream, cr_resident_grid(c, crsd_decode_kernel(), CRGPU_WAVE, 0, grid), D, m->L));

@@ -90,6 +90,8 @@ int  crgpu_set_stream(crgpu_ctx* ctx, void* hip_stream);
                                           decoder's workgroups leave room on a CU for a sorting kernel's 152 KB. Same bytes          */
 #define CRGPU_OPT_DICPICK_EPOCHS    10   /* crgpu_dicpick_dev: purges of the reference's word map replayed on the device before the
                                           stream goes to the host census instead (default 256; 0: always the host census)  */
+#define CRGPU_OPT_SEQDEC_GRID       11   /* at most this many workgroups for k_seqdec_v5 (0 = no limit): with fewer than there are
+                                          sequences a wave takes a second sequence from the ticket in the same launch       */
 int  crgpu_set_option(crgpu_ctx* ctx, int option, int value);
 
 /*

@@ -4,6 +4,7 @@ reference (oracle/_ref/*.so, when present) and the seeded input generators named
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg import this module.
 """
 import ctypes
+import functools
 import hashlib
 import os
 import subprocess
@@ -291,6 +292,31 @@ class Reference:
     def encode(self, data):
         return self._run(self.L.lzencode, data)
 
+    def _run_sequence(self, fn, blocks):
+        """reset_models() ONCE, then block after block through data_block_t: the models are carried as the reference's own
+        main() carries them over the datablocks of a file"""
+        L = self.L
+        L.reset_models()
+        out = []
+        for data in blocks:
+            ib, ob = DataBlock(), DataBlock()
+            L.data_block_resize(ctypes.byref(ib), len(data))
+            if len(data):
+                ctypes.memmove(ib.m_data, bytes(data), len(data))
+            L.data_block_resize(ctypes.byref(ob), 0)
+            fn(ctypes.byref(ib), ctypes.byref(ob), 0)
+            out.append(ctypes.string_at(ob.m_data, ob.m_size))
+            L.data_block_destroy(ctypes.byref(ib))
+            L.data_block_destroy(ctypes.byref(ob))
+        return out
+
+    def encode_sequence(self, blocks):
+        return self._run_sequence(self.L.lzencode, blocks)
+
+    def decode_sequence(self, coded):
+        """The reference decoder trusts its input: feed it nothing behind a stored block of 16 bytes or more."""
+        return self._run_sequence(self.L.lzdecode, coded)
+
     # --- dictionary stage (file-scope statics in the reference: one dictionary per loaded copy) ---
     @classmethod
     def private_copy(cls, which="rop"):
@@ -537,3 +563,134 @@ def gen_stored_boundary(encode, is_stored=lambda e: e[0] == 0, sizes=((1200, 1),
         for r in range(max(0, hi - around), min(n, hi + around) + 1):
             blocks.append(noise[:r] + text[: n - r])
     return blocks
+
+
+# ---- dependent-block (carried) comprop sequences: the hand-made cases and a seeded generator -----------------------
+# Shared by the CPU anchor (test_oracle.py: oracle == reference library, per sequence) and the GPU tests of the carried
+# paths (test_gpu_carry.py, test_gpu_seq.py, test_gpu_seqdec.py, test_gpu_seq_fuzz.py: GPU == oracle).
+
+@functools.lru_cache(maxsize=None)
+def _carried_material():
+    T = gen_text
+    t3 = T(12288, 41)
+    A, B, C = t3[:4096], t3[4096:8192], t3[8192:]
+    o1 = [bytes([x, 0x6E, 0x21]) for x in range(256)]           # 256 contexts (x, 'n') that all escape to '!' in row 'n'
+    n62 = [bytes([65, 66, s]) for s in range(100, 190)]          # context "AB" meets 90 different bytes
+    cases = [
+        ("text3", [A, B, C]),                                     # nodes, order-3 entries and rows all met again
+        ("repeat", [A, B, B]),                                    # carried predictions are right from the first event
+        ("o2_halving", [b"ab" * 180, b"ab" * 180]),               # count(256) of "ab" / "ba" passes 250 in block 2 only with block 1's hits
+        ("o1_255", [b"".join(o1[:130]), b"".join(o1[130:])]),     # row 'n', byte '!': 1 + 254 escapes = 255 in block 2
+        ("node62", [b"".join(n62[:45]), b"".join(n62[45:])]),     # a node that passes 62 symbols across the boundary
+        ("tiny_between", [A, b"", B[:15], C]),                    # under 16 bytes: models and context untouched
+        ("stored_between", [A, gen_rand(2048, seed=9), B]),       # ends stored: the models stay at the abort point
+        ("families", [T(20000, 42), T(40000, 43), T(70000, 44)]),  # 28 KiB LDS kernels, the lds64 kernels, table sweeps + ticket walkers
+    ]
+    return {"A": A, "B": B, "C": C, "CASES": cases}
+
+
+def __getattr__(name):                      # A, B, C, CASES: generated on first use, so that importing this module stays cheap
+    if name in ("A", "B", "C", "CASES"):
+        return _carried_material()[name]
+    raise AttributeError(name)
+
+
+def carried_boundary_cases(encode):
+    """blocks whose coded size sits at the stored rule's boundary (one byte either side of the flip), each followed by text;
+    `encode` is an oracle's fresh-model encoder"""
+    return [("boundary%d" % k, [blk, _carried_material()["B"]]) for k, blk in
+            enumerate(gen_stored_boundary(encode, sizes=((1200, 1),), around=1))]
+
+
+FUZZ_EDGES = [0, 1, 8, 9, 10, 15, 16, 17, 63, 64, 65, 1023, 1024, 1025, 1033, 1034, 1040, 1088, 1089, 2047, 2048, 4097]
+
+
+def fuzz_block(rng, kind, n, text=gen_text):
+    """One block of the fuzz tests; `text(n, seed=)` supplies the text of kinds 0 and 4."""
+    if kind == 0:
+        return text(n, seed=int(rng.integers(1, 1 << 30)))
+    if kind == 1:                                       # k-symbol noise: few distinct contexts, many table hits
+        k = int(rng.choice([2, 3, 4, 16]))
+        return bytes(rng.integers(97, 97 + k, size=n, dtype=np.uint8))
+    if kind == 2:                                       # noise: every context new
+        return bytes(rng.integers(0, 256, size=n, dtype=np.uint8))
+    if kind == 3:                                       # runs of random length
+        out = bytearray()
+        while len(out) < n:
+            out += bytes([int(rng.integers(0, 256))]) * int(rng.integers(1, 400))
+        return bytes(out[:n])
+    if kind == 4:                                       # a phrase repeated with mutations (long matches, overlaps)
+        phrase = bytearray(text(int(rng.integers(5, 300)), seed=int(rng.integers(1, 1 << 30))))
+        out = bytearray()
+        while len(out) < n:
+            if rng.random() < 0.3 and phrase:
+                phrase[int(rng.integers(0, len(phrase)))] = int(rng.integers(32, 127))
+            out += phrase
+        return bytes(out[:n])
+    return gen_markov(n, int(rng.integers(0, 50)))
+
+
+@functools.lru_cache(maxsize=None)
+def _text_pool():
+    return gen_text(1 << 20, seed=77)
+
+
+def _pool_text(n, seed):
+    """n bytes of text from a place in one shared 1 MiB pool (gen_text costs the same for 100 bytes as for a megabyte)"""
+    pool = _text_pool()
+    at = seed % (len(pool) - n)
+    return pool[at:at + n]
+
+
+def _carried_size(rng, decodable):
+    u = rng.random()
+    if not decodable:
+        if u < 1 / 3:
+            return int(rng.choice(FUZZ_EDGES))
+        return int(rng.integers(0, 3000)) if u < 2 / 3 else int(rng.integers(3000, 6000))
+    # a small block carries a 20-byte header and tends to end stored: mostly under 16 bytes or above 1 KiB
+    if u < 0.2:
+        return int(rng.integers(0, 16))
+    if u < 0.3:
+        return int(rng.choice(FUZZ_EDGES))
+    return int(rng.choice(FUZZ_EDGES[11:])) if u < 0.45 else int(rng.integers(1023, 6000))
+
+
+@functools.lru_cache(maxsize=None)
+def gen_carried_sequences(seed, nseq, max_blocks, decodable=False):
+    """nseq sequences of 0 .. max_blocks dependent comprop blocks of fuzz_block's kinds (one in eight sequences has under four
+    blocks, where max_blocks allows). decodable=False: blocks that end stored may sit anywhere, back to back included.
+    decodable=True: a block of 16 bytes or more that the oracle codes as stored IN ITS SEQUENCE is drawn again from the same
+    generator unless it is the last one, so every sequence decodes in full (behind a stored block of 16 bytes or more no
+    decoder of the format follows the encoder's models: test_gpu_carry.py). Cached: callers leave the result alone."""
+    rng = np.random.default_rng(seed)
+    o = Oracle() if decodable else None
+    seqs = []
+    for _ in range(nseq):
+        if max_blocks >= 4 and rng.random() >= 1 / 8:
+            nb = int(rng.integers(4, max_blocks + 1))
+        else:
+            nb = int(rng.integers(0, min(3, max_blocks) + 1))
+        blocks = []
+        for i in range(nb):
+            for _try in range(64):
+                b = fuzz_block(rng, int(rng.integers(0, 6)), _carried_size(rng, decodable), text=_pool_text)
+                if not decodable or len(b) < 16 or i == nb - 1:
+                    break
+                if o.rop_encode(b, reset=(i == 0))[0] != 0:
+                    break
+                for k, p in enumerate(blocks):          # the stored attempt left the oracle's models at its abort point: replay
+                    o.rop_encode(p, reset=(k == 0))
+            else:
+                raise AssertionError("no block that codes behind %d blocks in 64 draws" % i)
+            blocks.append(b)
+        seqs.append(blocks)
+    return seqs
+
+
+def first_stored(coded, blocks):
+    """index of the first block of 16 bytes or more that ended stored, or None"""
+    for i, (e, b) in enumerate(zip(coded, blocks)):
+        if e[0] == 0 and len(b) >= 16:
+            return i
+    return None

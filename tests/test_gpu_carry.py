@@ -13,30 +13,11 @@ import pytest
 
 import crlib
 from comprox_amd import api
+from crlib import A, B, C, CASES          # the carried case material, shared with the CPU anchor in test_oracle.py
 
 pytestmark = pytest.mark.gpu
 
 T = crlib.gen_text
-_t3 = T(12288, 41)
-A, B, C = _t3[:4096], _t3[4096:8192], _t3[8192:]
-_o1 = [bytes([x, 0x6E, 0x21]) for x in range(256)]           # 256 contexts (x, 'n') that all escape to '!' in row 'n'
-_n62 = [bytes([65, 66, s]) for s in range(100, 190)]          # context "AB" meets 90 different bytes
-CASES = [
-    ("text3", [A, B, C]),                                     # nodes, order-3 entries and rows all met again
-    ("repeat", [A, B, B]),                                    # carried predictions are right from the first event
-    ("o2_halving", [b"ab" * 180, b"ab" * 180]),               # count(256) of "ab" / "ba" passes 250 in block 2 only with block 1's hits
-    ("o1_255", [b"".join(_o1[:130]), b"".join(_o1[130:])]),   # row 'n', byte '!': 1 + 254 escapes = 255 in block 2
-    ("node62", [b"".join(_n62[:45]), b"".join(_n62[45:])]),   # a node that passes 62 symbols across the boundary
-    ("tiny_between", [A, b"", B[:15], C]),                    # under 16 bytes: models and context untouched
-    ("stored_between", [A, crlib.gen_rand(2048, seed=9), B]),  # ends stored: the models stay at the abort point
-    ("families", [T(20000, 42), T(40000, 43), T(70000, 44)]),  # 28 KiB LDS kernels, the lds64 kernels, table sweeps + ticket walkers
-]
-
-
-def _boundary_cases(oracle):
-    """blocks whose coded size sits at the stored rule's boundary (one byte either side of the flip), each followed by text"""
-    return [("boundary%d" % k, [blk, B]) for k, blk in
-            enumerate(crlib.gen_stored_boundary(oracle.rop_encode, sizes=((1200, 1),), around=1))]
 
 
 def _expect(oracle, blocks):
@@ -86,7 +67,7 @@ def _decode_carried(blocks):
 @pytest.mark.parametrize("tables", [0, 1], ids=["lds", "tables"])
 @pytest.mark.parametrize("name", [c[0] for c in CASES] + ["boundary0", "boundary1", "boundary2", "reset_mid", "dev"])
 def test_carried_blocks_equal_the_reference_sequence(gpu, oracle, name, tables):
-    blocks = dict(CASES + _boundary_cases(oracle) + [("reset_mid", [A, B]), ("dev", [A, b"", crlib.gen_rand(2048, seed=9), B, T(30000, 45)])])[name]
+    blocks = dict(CASES + crlib.carried_boundary_cases(oracle.rop_encode) + [("reset_mid", [A, B]), ("dev", [A, b"", crlib.gen_rand(2048, seed=9), B, T(30000, 45)])])[name]
     want = _expect(oracle, blocks)
     models = gpu.models_create()
     gpu.set_option(api.OPT_LZP_TABLES, tables)

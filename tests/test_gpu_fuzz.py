@@ -11,32 +11,11 @@ from comprox_amd import CODEC_ROP, CODEC_ROX, CODEC_ROLZ
 pytestmark = pytest.mark.gpu
 
 
-def _block(rng, kind, n):
-    if kind == 0:
-        return crlib.gen_text(n, seed=int(rng.integers(1, 1 << 30)))
-    if kind == 1:                                       # k-symbol noise: few distinct contexts, many table hits
-        k = int(rng.choice([2, 3, 4, 16]))
-        return bytes(rng.integers(97, 97 + k, size=n, dtype=np.uint8))
-    if kind == 2:                                       # noise: every context new
-        return bytes(rng.integers(0, 256, size=n, dtype=np.uint8))
-    if kind == 3:                                       # runs of random length
-        out = bytearray()
-        while len(out) < n:
-            out += bytes([int(rng.integers(0, 256))]) * int(rng.integers(1, 400))
-        return bytes(out[:n])
-    if kind == 4:                                       # a phrase repeated with mutations (long matches, overlaps)
-        phrase = bytearray(crlib.gen_text(int(rng.integers(5, 300)), seed=int(rng.integers(1, 1 << 30))))
-        out = bytearray()
-        while len(out) < n:
-            if rng.random() < 0.3 and phrase:
-                phrase[int(rng.integers(0, len(phrase)))] = int(rng.integers(32, 127))
-            out += phrase
-        return bytes(out[:n])
-    return crlib.gen_markov(n, int(rng.integers(0, 50)))
+_block = crlib.fuzz_block                   # (rng, kind, n): shared with crlib.gen_carried_sequences
 
 
 def _sizes(rng, count):
-    edges = [0, 1, 8, 9, 10, 15, 16, 17, 63, 64, 65, 1023, 1024, 1025, 1033, 1034, 1040, 1088, 1089, 2047, 2048, 4097]
+    edges = crlib.FUZZ_EDGES
     out = [int(rng.choice(edges)) for _ in range(count // 3)]
     out += [int(rng.integers(0, 3000)) for _ in range(count // 3)]
     out += [int(rng.integers(3000, 40000)) for _ in range(count - len(out))]

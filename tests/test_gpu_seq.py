@@ -6,7 +6,7 @@ import pytest
 
 import crlib
 from comprox_amd import api
-from test_gpu_carry import A, B, C, CASES
+from crlib import A, B, C, CASES
 
 pytestmark = pytest.mark.gpu
 

@@ -7,7 +7,7 @@ import pytest
 
 import crlib
 from comprox_amd import api
-from test_gpu_carry import A, B, C, CASES
+from crlib import A, B, C, CASES
 
 pytestmark = pytest.mark.gpu
 
@@ -97,6 +97,89 @@ def test_more_dense_nodes_than_lds_holds_across_a_boundary(gpu, oracle, calls):
     finally:
         ds.close()
     assert got == DENSE2
+
+
+# the same over forty other contexts (65 + c, 67): a second sequence whose dense nodes fill the wave's LDS
+DENSEB = b"".join(bytes([65 + c, 67, s]) for c in range(40) for s in range(100, 190))
+
+
+@pytest.mark.parametrize("cap", [0, 1, 2])
+def test_a_wave_that_takes_a_second_sequence(gpu, oracle, cap):
+    """k_seqdec_v5 is launched with min(resident, sequences) workgroups, and thousands are resident: without a cap no wave ever
+    goes round its ticket loop twice. CRGPU_OPT_SEQDEC_GRID = 1 makes ONE wave walk every sequence of a launch in the order
+    of the ticket (most coded bytes first; asserted below), so each pick-up meets the LDS the sequence before it left:
+      call 1   slot 0: DENSE2[0] (20 dense nodes), slots 1 and 2: A
+      call 2   slot 3, fresh: DENSEB, 40 dense nodes, the LDS copies all its own
+               slot 0 continues with DENSE2[1]: not fresh; 20 copies come back from the arena, LDS slots 20 .. 31 still hold
+                      slot 3's until this block's own nodes take them, and the counter passes CR_V5_DLDS = 32 in the block
+               slot 1 continues with B and a piece of C: not fresh, no dense node of its own, the LDS full of the others'
+               slot 4, fresh: text, a block that is stored, text — fresh pick-ups reload nothing
+               slot 5, fresh: its second block fails through the header's `total > cap` path (no damaged stream is run);
+                      that block and the one behind it are None, and
+               slot 2, picked up behind it, continues as if nothing had happened; slot 6 has no block
+      call 3   slot 0 with all of DENSE again, then slot 3 with the head of DENSEB: both not fresh with a counter of 40, so the
+               copies 0 .. 31 come back over the other's and the nodes 32 .. 39 are met in the arena
+    All caps must give the oracle's bytes."""
+    a, b, c = A[:1200], B[:1200], C[:1200]
+    a2, b2, x = A[:2000], B[:2000], crlib.gen_rand(256, seed=9)
+    plain = [DENSE2 + [DENSE], [A, B, C[:3000]], [A, B[:1000]], [DENSEB, DENSEB[:5400]], [a2, x, b2], [a, b, c], []]
+    coded = [_enc(oracle, s) for s in plain]
+    coded[4] = _enc(oracle, [a2, b2])                           # lzdecode leaves the models alone on a stored block: the text
+    coded[4].insert(1, oracle.rop_encode(x))                    # behind it continues the text in front of it
+    assert coded[4][1][0] == 0 and len(coded[4][1]) == 276
+    assert all(e[0] == 1 for s in (0, 1, 2, 3, 5) for e in coded[s])
+    want = [_dec(oracle, e, [len(p) for p in s]) for e, s in zip(coded, plain)]
+    assert want == plain
+    cut = [(1, 2), (1, 3), (1, 2), (0, 1), (0, 3), (0, 3), (0, 0)]          # blocks of calls 1 and 2 per slot; call 3 has the rest
+    calls = [[e[:i] for e, (i, j) in zip(coded, cut)], [e[i:j] for e, (i, j) in zip(coded, cut)], [e[j:] for e, (i, j) in zip(coded, cut)]]
+    sums = [[sum(map(len, seq)) for seq in call] for call in calls]
+    walk = [sorted((s for s in range(7) if call[s]), key=lambda s: -sums[k][s]) for k, call in enumerate(calls)]
+    assert walk[1] == [3, 0, 1, 4, 5, 2] and walk[2] == [0, 3]
+    assert all(sums[k][p] > sums[k][q] for k in (1, 2) for p, q in zip(walk[k], walk[k][1:])), "no ties: the order is the sizes'"
+    caps = [[[len(p) for p in s[:i]] for s, (i, j) in zip(plain, cut)], [[len(p) for p in s[i:j]] for s, (i, j) in zip(plain, cut)],
+            [[len(p) for p in s[j:]] for s, (i, j) in zip(plain, cut)]]
+    caps[1][5][1] -= 1                                          # slot 5, second block: one byte too little room
+    ds = gpu.decode_set_create(7, len(DENSE))
+    gpu.set_option(api.OPT_SEQDEC_GRID, cap)
+    try:
+        got = [gpu.decode_sequences(calls[0], caps[0], ds)]
+        print("dense nodes behind call 1:", [ds.dense_nodes(s) for s in range(7)])
+        got.append(gpu.decode_sequences(calls[1], caps[1], ds, strict=False))
+        print("dense nodes behind call 2:", [ds.dense_nodes(s) for s in range(7)])
+        assert ds.dense_nodes(0) > 32 and ds.dense_nodes(3) > 32
+        got.append(gpu.decode_sequences(calls[2], caps[2], ds))
+    finally:
+        gpu.set_option(api.OPT_SEQDEC_GRID, 0)
+        ds.close()
+    for s, (i, j) in enumerate(cut):
+        w = [want[s][:i], want[s][i:j], want[s][j:]]
+        if s == 5:
+            w[1] = [a, None, None]
+        for k in range(3):
+            assert got[k][s] == w[k], f"cap {cap}: call {k + 1}, slot {s}: blocks {[n for n, (p, q) in enumerate(zip(got[k][s], w[k])) if p != q]} differ"
+
+
+def test_fifteen_resets_of_one_slot(gpu, oracle):
+    """A slot's order-3 generation has four bits: cr_v3_reset wipes the slot's 8 MiB table when it wraps, which in a decode
+    set happens on one slot's sixteenth reset. Slot 0 decodes [A, B] seventeen times, reset in front of each (the set's
+    creation was its first reset); slot 1 decodes A in the first round, B in the ninth and C in the last with no reset
+    in between — its generations must not move with its neighbour's. (The node generation has sixteen bits: its wrap would
+    take 65 536 resets of one slot and is left out.)"""
+    coded, n = _enc(oracle, [A, B, C]), len(A)
+    assert _dec(oracle, coded, [n, n, n]) == [A, B, C]
+    other = {0: 0, 8: 1, 16: 2}
+    got1 = []
+    ds = gpu.decode_set_create(2, 4096)
+    try:
+        for r in range(17):
+            ds.reset([0])
+            mine = [coded[other[r]]] if r in other else []
+            got = gpu.decode_sequences([coded[:2], mine], [[n, n], [n] * len(mine)], ds)
+            assert got[0] == [A, B], f"round {r}: slot 0, blocks {[i for i, (p, q) in enumerate(zip(got[0], [A, B])) if p != q]} differ"
+            got1 += got[1]
+    finally:
+        ds.close()
+    assert got1 == [A, B, C], f"slot 1: blocks {[i for i, (p, q) in enumerate(zip(got1, [A, B, C])) if p != q]} differ"
 
 
 def test_device_pointer_entry_point_with_gaps(gpu, oracle):

@@ -203,6 +203,51 @@ def test_rop_oracle_equals_reference_random():
         assert ref.decode(e) == d
 
 
+CARRIED_FUZZ_SEEDS = (31, 32)
+
+
+def _carried_anchor_inputs(o):
+    hand = [(name, blocks) for name, blocks in crlib.CASES + crlib.carried_boundary_cases(o.rop_encode)]
+    fuzz = [("seed%d/%d" % (seed, k), blocks) for seed in CARRIED_FUZZ_SEEDS
+            for k, blocks in enumerate(crlib.gen_carried_sequences(seed, 16, 10))]
+    return hand, fuzz
+
+
+@pytest.mark.skipif(not crlib.Reference.available("rop"), reason="oracle/_ref not built (no /root/reference)")
+def test_rop_oracle_equals_reference_carried():
+    """Carried mode (reset_models() in front of the first block only) against the unmodified reference library, sequence by
+    sequence: the hand-made cases of the GPU tests, the stored rule's boundary blocks and two seeds of generated sequences, in
+    which blocks that end stored sit first, last, mid-sequence and back to back. Encode: every block, those behind stored ones
+    included (the models stay at the abort point). Decode: up to and including the first stored block of 16 bytes or more —
+    behind it the encoder's models are not the decoder's, and the reference decoder trusts its input."""
+    ref = crlib.Reference("rop")
+    o = crlib.Oracle()
+    hand, fuzz = _carried_anchor_inputs(o)
+    stored_pair = stored_first = tiny_between = 0
+    for name, blocks in hand + fuzz:
+        is_fuzz = name.startswith("seed")
+        want = ref.encode_sequence(blocks)
+        got = [o.rop_encode(b, reset=(i == 0)) for i, b in enumerate(blocks)]
+        for i, (g, w) in enumerate(zip(got, want)):
+            assert g == w, f"{name}: encoded block {i} of {len(blocks)} differs ({len(g)} bytes, the reference has {len(w)})"
+        assert len(got) == len(want) == len(blocks)
+        cut = crlib.first_stored(want, blocks)
+        upto = len(blocks) if cut is None else cut + 1
+        plain = [bytes(b) for b in blocks[:upto]]
+        assert ref.decode_sequence(want[:upto]) == plain, f"{name}: the reference does not decode its own sequence"
+        back = [o.rop_decode(e, len(b), reset=(i == 0)) for i, (e, b) in enumerate(zip(want[:upto], plain))]
+        for i, (g, w) in enumerate(zip(back, plain)):
+            assert g == w, f"{name}: decoded block {i} of {upto} differs"
+        if is_fuzz:
+            st = [e[0] == 0 and len(b) >= 16 for e, b in zip(want, blocks)]
+            coded = [e[0] != 0 for e in want]
+            stored_pair += sum(a and b for a, b in zip(st, st[1:]))
+            stored_first += bool(st and st[0])
+            tiny_between += sum(coded[i - 1] and 1 <= len(blocks[i]) <= 15 and coded[i + 1] for i in range(1, len(blocks) - 1))
+    # what the generated sequences are there for; without these the seeds are the wrong ones
+    assert stored_pair >= 1 and stored_first >= 1 and tiny_between >= 1, (stored_pair, stored_first, tiny_between)
+
+
 def test_parse_tail_rule(oracle):
     """No prediction is attempted within 1024 bytes of the end (ropmain/cr-coder.c:103)."""
     d = crlib.gen_fox(5000)
