@@ -118,6 +118,8 @@ def load_library():
     L.crgpu_encode_sequences_carried.argtypes = [vp, i32, vp, vp, vp, vp, vp, u32, vp, vp, vp]
     L.crgpu_decode_set_create.restype = i32
     L.crgpu_decode_set_create.argtypes = [vp, u32, u32, ctypes.POINTER(vp)]
+    L.crgpu_decode_set_create_codec.restype = i32
+    L.crgpu_decode_set_create_codec.argtypes = [vp, i32, u32, u32, ctypes.POINTER(vp)]
     L.crgpu_decode_set_destroy.restype = None
     L.crgpu_decode_set_destroy.argtypes = [vp]
     L.crgpu_decode_set_reset.restype = i32
@@ -392,8 +394,8 @@ class CrGpu:
                                                                 len(seq_first) - 1, d_out, d_out_off, d_out_size),
                     "crgpu_encode_sequences_carried_dev")
 
-    def decode_set_create(self, nseq: int, max_block: int) -> "CrDecodeSet":
-        return CrDecodeSet(self, nseq, max_block)
+    def decode_set_create(self, nseq: int, max_block: int, codec: int = CODEC_ROP) -> "CrDecodeSet":
+        return CrDecodeSet(self, nseq, max_block, codec)
 
     def decode_sequences(self, sequences, caps, decode_set: "CrDecodeSet", strict: bool = True, codec: int = CODEC_ROP):
         """sequences: list of lists of encoded blocks, sequence s on slot s of the set; caps: the room for every decoded block,
@@ -656,13 +658,15 @@ class CrModelSet:
 
 
 class CrDecodeSet:
-    """`nseq` decoder models of comprop in the batched decoder's own format (crgpu_decode_set), one slot per sequence of dependent blocks."""
+    """`nseq` decoder models of one codec in the batched decoder's own format (crgpu_decode_set), one slot per sequence of dependent
+    blocks; decode_sequences on it names the same codec."""
 
-    def __init__(self, gpu: CrGpu, nseq: int, max_block: int):
+    def __init__(self, gpu: CrGpu, nseq: int, max_block: int, codec: int = CODEC_ROP):
         self.gpu = gpu
         self.nseq = nseq
+        self.codec = codec
         self.h = ctypes.c_void_p()
-        gpu._check(gpu.lib.crgpu_decode_set_create(gpu.h, nseq, max_block, ctypes.byref(self.h)), "crgpu_decode_set_create")
+        gpu._check(gpu.lib.crgpu_decode_set_create_codec(gpu.h, codec, nseq, max_block, ctypes.byref(self.h)), "crgpu_decode_set_create_codec")
 
     def reset(self, which=None):
         """every slot, or the slots listed in `which`, back to the state of reset_models() (and no longer poisoned)"""

@@ -963,7 +963,7 @@ struct crgpu_ctx {
     int         one_wave_encoder;   /* CRGPU_OPT_ONE_WAVE_ENCODER: the model-carrying one-wave coders instead of the kernel pipeline */
     int         one_wave_decoder;   /* CRGPU_OPT_ONE_WAVE_DECODER: the model-carrying C++ decoders instead of the assembly step */
     uint32_t    lzp_grid, match_grid;   /* experiments: at most this many workgroups for the pre-pass kernels (0 = no limit) */
-    uint32_t    seqdec_grid;            /* the same for k_seqdec_v5: its waves then walk several sequences in one launch */
+    uint32_t    seqdec_grid;            /* the same for the k_seqdec kernels: their waves then walk several sequences in one launch */
     int         decoder_helper;     /* CRGPU_OPT_DECODER_HELPER: comprop's batched decoder with a helper wave per block (k_rop_decode_v5h) */
     int         decoder_small_lds;  /* CRGPU_OPT_DECODER_LDS_NODES 0: k_rop_decode_v5s, no dense nodes in LDS */
     struct { const void* k; uint32_t dyn; int per_cu; } occ[48];   /* cr_resident_grid: workgroups per CU the runtime reports, per kernel */
@@ -1970,6 +1970,7 @@ extern "C" int crgpu_encode_sequences_carried_dev(crgpu_ctx* c, int codec, crgpu
 struct crgpu_decode_set {
     crgpu_ctx*    ctx;
     uint32_t      nseq, max_block;
+    int           codec;       /* whose models the slots hold: the calls on the set must name it */
     CrArenaLayout L;           /* of one slot; L.max_block is the set's own (the tables are sized for it rounded up to 1 KiB) */
     uint8_t*      d_store;     /* nseq x L.stride */
     uint32_t*     d_idx;       /* 3 x nseq + 1 words: a call's seq_first, its order, a reset's list */
@@ -2005,16 +2006,22 @@ extern "C" void crgpu_decode_set_destroy(crgpu_decode_set* m) {
     free(m);
 }
 
-extern "C" int crgpu_decode_set_create(crgpu_ctx* c, uint32_t nseq, uint32_t max_block, crgpu_decode_set** out) {
+static const char* sd_codec_name(int codec) { return codec == CRGPU_CODEC_ROP ? "comprop" : codec == CRGPU_CODEC_ROX ? "comprox" : codec == CRGPU_CODEC_ROLZ ? "comprolz" : "an unknown codec"; }
+
+/* beside the models a slot holds its codec's matcher tables as the batched decoders use them (launch()) and, for comprox and
+ * comprolz, the keep area their side models are parked in between calls */
+extern "C" int crgpu_decode_set_create_codec(crgpu_ctx* c, int codec, uint32_t nseq, uint32_t max_block, crgpu_decode_set** out) {
     if (!c || !out) return CRGPU_E_ARG;
     *out = NULL;
+    if (codec != CRGPU_CODEC_ROP && codec != CRGPU_CODEC_ROX && codec != CRGPU_CODEC_ROLZ) { snprintf(c->err, sizeof c->err, "codec %d not available", codec); return CRGPU_E_ARG; }
+    const uint32_t use = CR_USE_DMODEL | (codec == CRGPU_CODEC_ROP ? CR_USE_LZP | CR_USE_LZ2 : codec == CRGPU_CODEC_ROX ? CR_USE_KEEP : CR_USE_KEEP | CR_USE_CAND | CR_USE_HIST | CR_USE_RHEAD);
     if (nseq == 0 || nseq > 65535u || max_block > CRGPU_MAX_BLOCK + 1u) { snprintf(c->err, sizeof c->err, "a decode set has 1 .. 65535 slots for blocks of up to CRGPU_MAX_BLOCK + 1 bytes"); return CRGPU_E_ARG; }
-    const CrArenaLayout L = make_layout((uint32_t)align_up(max_block < 1024u ? 1024u : max_block, 1024u), CR_USE_DMODEL | CR_USE_LZP | CR_USE_LZ2, CR_SD_DENSE_SLOTS);
+    const CrArenaLayout L = make_layout((uint32_t)align_up(max_block < 1024u ? 1024u : max_block, 1024u), use, CR_SD_DENSE_SLOTS);
     if (L.stride == 0) { snprintf(c->err, sizeof c->err, "the decoder's layout cannot address the tables of %u-byte blocks", max_block); return CRGPU_E_ARG; }
     CR_TRY(c, hipSetDevice(c->device));
     crgpu_decode_set* m = (crgpu_decode_set*)calloc(1, sizeof *m);
     if (!m) return CRGPU_E_NOMEM;
-    m->ctx = c; m->nseq = nseq; m->max_block = max_block; m->L = L; m->L.max_block = max_block;
+    m->ctx = c; m->nseq = nseq; m->max_block = max_block; m->codec = codec; m->L = L; m->L.max_block = max_block;
     const size_t words = 3u * (size_t)nseq + 1u;
     if (hipMalloc((void**)&m->d_store, (size_t)(nseq * L.stride)) != hipSuccess || hipMalloc((void**)&m->d_idx, words * 4u) != hipSuccess ||
         hipHostMalloc((void**)&m->h_idx, words * 4u, hipHostMallocDefault) != hipSuccess) {
@@ -2029,6 +2036,10 @@ extern "C" int crgpu_decode_set_create(crgpu_ctx* c, uint32_t nseq, uint32_t max
     if (rc != CRGPU_OK) { crgpu_decode_set_destroy(m); return rc; }
     *out = m;
     return CRGPU_OK;
+}
+
+extern "C" int crgpu_decode_set_create(crgpu_ctx* c, uint32_t nseq, uint32_t max_block, crgpu_decode_set** out) {
+    return crgpu_decode_set_create_codec(c, CRGPU_CODEC_ROP, nseq, max_block, out);
 }
 
 /* diagnostic: how many order-2 nodes of slot `slot` live in the dense area (the step's counter); waits for the stream */
@@ -2048,7 +2059,7 @@ extern "C" int crgpu_decode_sequences_carried_dev(crgpu_ctx* c, int codec, crgpu
                                                   const uint32_t* in_size, const uint32_t* seq_first, uint32_t nseq,
                                                   uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_size, int sync) {
     if (!c || !m || m->ctx != c || (nseq && !seq_first)) return CRGPU_E_ARG;
-    if (codec != CRGPU_CODEC_ROP) { snprintf(c->err, sizeof c->err, "models are carried for comprop only (codec %d)", codec); return CRGPU_E_ARG; }
+    if (codec != m->codec) { snprintf(c->err, sizeof c->err, "%s blocks (codec %d) for a decode set of %s (codec %d)", sd_codec_name(codec), codec, sd_codec_name(m->codec), m->codec); return CRGPU_E_ARG; }
     if (nseq > m->nseq) { snprintf(c->err, sizeof c->err, "%u sequences for a set of %u slots", nseq, m->nseq); return CRGPU_E_ARG; }
     for (uint32_t s = 0; s < nseq; s++) if (seq_first[s + 1u] < seq_first[s]) { snprintf(c->err, sizeof c->err, "seq_first descends at sequence %u", s); return CRGPU_E_ARG; }
     const uint32_t first = nseq ? seq_first[0] : 0u, nb = nseq ? seq_first[nseq] - first : 0u;
@@ -2062,7 +2073,7 @@ extern "C" int crgpu_decode_sequences_carried_dev(crgpu_ctx* c, int codec, crgpu
     hipError_t e = hipMemcpyAsync(h_size, in_size + first, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);            /* (also: the set's pinned tables are free again) */
     if (e != hipSuccess) { free(h); return fail(c, e, "hipMemcpyAsync(block sizes)"); }
-    const uint32_t room = crgpu_bound(CRGPU_CODEC_ROP, m->max_block);
+    const uint32_t room = crgpu_bound(m->codec, m->max_block);
     for (uint32_t b = 0; b < nb; b++) if (h_size[b] > room) {
         snprintf(c->err, sizeof c->err, "coded block of %u bytes, a block of the set's %u bytes codes to %u at most", h_size[b], m->max_block, room);
         free(h); return CRGPU_E_ARG;
@@ -2088,7 +2099,8 @@ extern "C" int crgpu_decode_sequences_carried_dev(crgpu_ctx* c, int codec, crgpu
     const uint32_t grid = c->seqdec_grid && c->seqdec_grid < na ? c->seqdec_grid : na;   /* experiment and tests: fewer workgroups than sequences, so a wave takes a second ticket */
     CR_CARRY_RC(carry_group_open(c));
     CR_TRY(c, hipEventRecord(c->ev0, c->stream));
-    CR_CARRY_STAGE("k_seqdec_v5", crsd_launch_decode(c->stream, cr_resident_grid(c, crsd_decode_kernel(), CRGPU_WAVE, 0, grid), D, m->L));
+    const int which = m->codec == CRGPU_CODEC_ROX ? CR_SD_ROX : m->codec == CRGPU_CODEC_ROLZ ? CR_SD_ROLZ : CR_SD_ROP;
+    CR_CARRY_STAGE(crsd_decode_name(which), crsd_launch_decode(c->stream, which, cr_resident_grid(c, crsd_decode_kernel(which), CRGPU_WAVE, 0, grid), D, m->L));
     CR_CARRY_RC(carry_group_close(c));
     CR_TRY(c, hipEventRecord(c->ev1, c->stream));
     c->timed = 1;
@@ -2466,7 +2478,7 @@ extern "C" int crgpu_decode_sequences_carried(crgpu_ctx* c, int codec, crgpu_dec
                                               const uint32_t* in_size, const uint32_t* seq_first, uint32_t nseq,
                                               uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_size) {
     if (!c || !m || (nseq && !seq_first)) return CRGPU_E_ARG;
-    if (codec != CRGPU_CODEC_ROP) { snprintf(c->err, sizeof c->err, "models are carried for comprop only (codec %d)", codec); return CRGPU_E_ARG; }
+    if (codec != m->codec) { snprintf(c->err, sizeof c->err, "%s blocks (codec %d) for a decode set of %s (codec %d)", sd_codec_name(codec), codec, sd_codec_name(m->codec), m->codec); return CRGPU_E_ARG; }
     for (uint32_t s = 0; s < nseq; s++) if (seq_first[s + 1u] < seq_first[s]) { snprintf(c->err, sizeof c->err, "seq_first descends at sequence %u", s); return CRGPU_E_ARG; }
     if (nseq == 0) return crgpu_decode_sequences_carried_dev(c, codec, m, NULL, NULL, NULL, NULL, 0, NULL, NULL, NULL, NULL, 0);
     uint32_t* rel = (uint32_t*)malloc(sizeof(uint32_t) * ((size_t)nseq + 1u));

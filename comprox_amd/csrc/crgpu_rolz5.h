@@ -14,8 +14,15 @@
 #include "crgpu_rop5.h"
 #include "crgpu_rolz.h"
 
+/* CARRY (crgpu_seqdec.h, as in cr_rop_decode_v5): the block continues its predecessor's models — the PPM tables in the arena and
+ * the two side models in `sh` — instead of resetting them; generations, context register and dense capacity come from `carry`,
+ * the register goes back there, the dense counter in the scratch line is left standing. The matcher is the block's own
+ * (matcher_init, cr-coder.c:321), and so are the range decoders; the block's raw first byte is written out and never pushed
+ * into the context (cr-coder.c:316-317), so the first symbol is decoded in the register the block before left. */
+template <int CARRY = 0>
 CR_DEV uint32_t cr_rolz_decode_v5(const uint8_t* src_, uint32_t n, uint8_t* dst_, uint32_t cap, const CrRolzTables& T, uint32_t* row_head,
-                                  uint8_t* arena_, const CrArenaLayout& L, CrRoxShared& sh, uint32_t* hist, uint32_t lds_scratch, u64* st) {
+                                  uint8_t* arena_, const CrArenaLayout& L, CrRoxShared& sh, uint32_t* hist, uint32_t lds_scratch, u64* st,
+                                  CrV5Carry* carry = nullptr) {
     const uint8_t* const src = cr_uni_ptr(src_);
     uint8_t* const dst = cr_uni_ptr(dst_);
     uint8_t* const arena = cr_uni_ptr(arena_);
@@ -36,9 +43,10 @@ CR_DEV uint32_t cr_rolz_decode_v5(const uint8_t* src_, uint32_t n, uint8_t* dst_
     if (total == 0 || total > cap || total > L.max_block || o_side < CR_ROLZ_HEADER || o_side > n) return 0xFFFFFFFFu;
     const bool ctx4 = total >= 4194304u;                                 /* using_ctx4, cr-coder.c:314 */
 
-    cr_rolz_side_reset(sh);
-    uint32_t g3_;
-    const uint32_t gen = cr_uni(cr_v3_reset(arena, L, g3_));
+    uint32_t g3_, gen_;
+    if constexpr (CARRY) { gen_ = carry->gen; g3_ = carry->g3; }
+    else { cr_rolz_side_reset(sh); gen_ = cr_v3_reset(arena, L, g3_); }
+    const uint32_t gen = cr_uni(gen_);
     const uint32_t g3 = cr_uni(g3_);
     cr_fill(reinterpret_cast<uint8_t*>(T.ring_head), (u64)CR_ROLZ_BUCKETS * 4u, 0u);     /* matcher_init */
     for (uint32_t k = lane; k < 256u; k += CRGPU_WAVE) row_head[k] = 0;
@@ -47,7 +55,8 @@ CR_DEV uint32_t cr_rolz_decode_v5(const uint8_t* src_, uint32_t n, uint8_t* dst_
      * reads them from the arena's scratch line (and writes the slot counter back there when it is left) */
     if (lane == 0) {
         uint32_t* scr = reinterpret_cast<uint32_t*>(arena + CRGPU_OFF_SCRATCH + 896u);
-        scr[0] = (uint32_t)L.off_dense; scr[1] = lds_scratch; scr[2] = 0u;
+        scr[0] = (uint32_t)L.off_dense; scr[1] = lds_scratch;
+        if constexpr (!CARRY) scr[2] = 0u;
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     cr_wave_sync();
@@ -64,6 +73,7 @@ CR_DEV uint32_t cr_rolz_decode_v5(const uint8_t* src_, uint32_t n, uint8_t* dst_
     uint32_t cache = cr_lane_get(win, 0), range = 0xFFFFFFFFu;
     uint32_t ib_hi = cr_lane_get(win, 1), ib_lo = cr_lane_get(win, 2), ibits = 64, widx = 3;
     uint32_t ctx = 0, have = 1, fed = 1, after_esc = 0;                  /* positions < fed are in the tables (or below 16: never fed) */
+    if constexpr (CARRY) ctx = cr_uni(carry->ctx);
     uint32_t x8_lo = 0, x8_hi = cr_uni((uint32_t)src[0]) << 24;          /* the 8 bytes in front of the write position */
     uint32_t pend_lo = 0, pend_hi = 0;                                   /* lane j: those 8 bytes for position fed + j */
     const uint32_t zero = 0;
@@ -77,7 +87,7 @@ CR_DEV uint32_t cr_rolz_decode_v5(const uint8_t* src_, uint32_t n, uint8_t* dst_
 #define CR_PF(acc_, ...) do { __VA_ARGS__; } while (0)
 #endif
 
-    const uint32_t dslots = cr_uni(L.dense_slots);
+    const uint32_t dslots = cr_uni(CARRY ? carry->dslots : L.dense_slots);
     while (have < total) {                                               /* cr-coder.c:334-375 */
         uint32_t ev, sym, pacc, pcnt;
         ctx = cr_uni(ctx); range = cr_uni(range); cache = cr_uni(cache); ib_lo = cr_uni(ib_lo); ib_hi = cr_uni(ib_hi); ibits = cr_uni(ibits);
@@ -191,6 +201,7 @@ CR_DEV uint32_t cr_rolz_decode_v5(const uint8_t* src_, uint32_t n, uint8_t* dst_
 #undef CR_PF
 #undef CR_FEED
     (void)st;
+    if constexpr (CARRY) carry->ctx = ctx;
     return have;
 }
 

@@ -16,8 +16,13 @@
 #include "crgpu_rop5.h"
 #include "crgpu_rox.h"
 
+/* CARRY (crgpu_seqdec.h, as in cr_rop_decode_v5): the block continues its predecessor's models — the PPM tables in the arena and
+ * the eight side models in `sh` — instead of resetting them; generations, context register and dense capacity come from `carry`,
+ * the register goes back there, the dense counter in the scratch line is left standing. The range decoders and prev_dist are
+ * the block's own (cr-coder.c:425-458). */
+template <int CARRY = 0>
 CR_DEV uint32_t cr_rox_decode_v5(const uint8_t* src_, uint32_t n, uint8_t* dst_, uint32_t cap, uint8_t* arena_,
-                                 const CrArenaLayout& L, CrRoxShared& sh, uint32_t lds_scratch) {
+                                 const CrArenaLayout& L, CrRoxShared& sh, uint32_t lds_scratch, CrV5Carry* carry = nullptr) {
     const uint8_t* const src = cr_uni_ptr(src_);
     uint8_t* const dst = cr_uni_ptr(dst_);
     uint8_t* const arena = cr_uni_ptr(arena_);
@@ -36,15 +41,17 @@ CR_DEV uint32_t cr_rox_decode_v5(const uint8_t* src_, uint32_t n, uint8_t* dst_,
     const uint32_t total = hw[0], o_spos = hw[4], o_pos = hw[5], o_len = hw[6];
     if (total > cap || total > L.max_block || o_spos < CR_ROX_HEADER || o_spos > o_pos || o_pos > o_len || o_len > n) return 0xFFFFFFFFu;
 
-    cr_side_reset(sh);
-    uint32_t g3_;
-    const uint32_t gen = cr_uni(cr_v3_reset(arena, L, g3_));
+    uint32_t g3_, gen_;
+    if constexpr (CARRY) { gen_ = carry->gen; g3_ = carry->g3; }
+    else { cr_side_reset(sh); gen_ = cr_v3_reset(arena, L, g3_); }
+    const uint32_t gen = cr_uni(gen_);
     const uint32_t g3 = cr_uni(g3_);
     /* where the dense slots start, the LDS address of the wave's 256 scratch bytes, the next free dense slot: the statement
      * reads them from the arena's scratch line (and writes the slot counter back there when it is left) */
     if (lane == 0) {
         uint32_t* scr = reinterpret_cast<uint32_t*>(arena + CRGPU_OFF_SCRATCH + 896u);
-        scr[0] = (uint32_t)L.off_dense; scr[1] = lds_scratch; scr[2] = 0u;
+        scr[0] = (uint32_t)L.off_dense; scr[1] = lds_scratch;
+        if constexpr (!CARRY) scr[2] = 0u;
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     cr_wave_sync();
@@ -64,10 +71,11 @@ CR_DEV uint32_t cr_rox_decode_v5(const uint8_t* src_, uint32_t n, uint8_t* dst_,
     uint32_t cache = cr_lane_get(win, 0), range = 0xFFFFFFFFu;
     uint32_t ib_hi = cr_lane_get(win, 1), ib_lo = cr_lane_get(win, 2), ibits = 64, widx = 3;
     uint32_t ctx = 0, have = 0, learned = 0, after_esc = 0, x8_lo = 0, x8_hi = 0, pend_lo = 0, pend_hi = 0;
+    if constexpr (CARRY) ctx = cr_uni(carry->ctx);
     const uint32_t zero = 0;
     uint32_t prev_dist = 0;
 
-    const uint32_t dslots = cr_uni(L.dense_slots);
+    const uint32_t dslots = cr_uni(CARRY ? carry->dslots : L.dense_slots);
     while (have < total) {                                               /* cr-coder.c:459-523 */
         uint32_t ev, sym, pacc, pcnt;
         /* (the side-stream code below leaves the compiler unsure that these are wave-uniform) */
@@ -144,6 +152,7 @@ CR_DEV uint32_t cr_rox_decode_v5(const uint8_t* src_, uint32_t n, uint8_t* dst_,
             have = cr_uni(have + 1u);
         }
     }
+    if constexpr (CARRY) carry->ctx = ctx;
     return have;
 }
 

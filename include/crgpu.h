@@ -90,7 +90,7 @@ int  crgpu_set_stream(crgpu_ctx* ctx, void* hip_stream);
                                           decoder's workgroups leave room on a CU for a sorting kernel's 152 KB. Same bytes          */
 #define CRGPU_OPT_DICPICK_EPOCHS    10   /* crgpu_dicpick_dev: purges of the reference's word map replayed on the device before the
                                           stream goes to the host census instead (default 256; 0: always the host census)  */
-#define CRGPU_OPT_SEQDEC_GRID       11   /* at most this many workgroups for k_seqdec_v5 (0 = no limit): with fewer than there are
+#define CRGPU_OPT_SEQDEC_GRID       11   /* at most this many workgroups for the k_seqdec kernels (0 = no limit): with fewer than there are
                                           sequences a wave takes a second sequence from the ticket in the same launch       */
 int  crgpu_set_option(crgpu_ctx* ctx, int option, int value);
 
@@ -181,6 +181,15 @@ int crgpu_encode_sequences_carried(crgpu_ctx* ctx, int codec, crgpu_model_set* s
  * (above CRGPU_MAX_BLOCK + 1); CRGPU_E_NOMEM when the allocation fails. The set belongs to its context. */
 typedef struct crgpu_decode_set crgpu_decode_set;
 int  crgpu_decode_set_create(crgpu_ctx* ctx, uint32_t nseq, uint32_t max_block, crgpu_decode_set** out);
+/* The same for any of the three codecs (crgpu_decode_set_create is this with CRGPU_CODEC_ROP); the set remembers its codec and
+ * serves calls that name it. A comprox / comprolz slot holds the same model tables and, in place of the LZP tables, an 8 KiB
+ * keep area for the side models (eight / two adaptive models of 256 symbols, parked there between calls) with its staging
+ * room; a comprolz slot also holds that codec's matcher — link tables, ring history (blocks up to 1 MiB), ring heads — emptied
+ * in front of every block as matcher_init does. Bytes per slot, M = max(1024, max_block rounded up to 1 KiB):
+ *   comprox   33 890 304 + 3 x (2 M + 256), rounded up to 4 KiB                      (34 287 616 for 64 KiB blocks)
+ *   comprolz  the same + 12 M + 32 M (M <= 1 MiB only) + 1 048 576                   (38 219 776 for 64 KiB blocks)
+ * CRGPU_E_ARG also for a codec that is none of the three. */
+int  crgpu_decode_set_create_codec(crgpu_ctx* ctx, int codec, uint32_t nseq, uint32_t max_block, crgpu_decode_set** out);
 void crgpu_decode_set_destroy(crgpu_decode_set* set);
 int  crgpu_decode_set_reset(crgpu_ctx* ctx, crgpu_decode_set* set, const uint32_t* which, uint32_t n);
 /* diagnostic: the order-2 nodes of a slot that have outgrown their line and live in its dense area; waits for the stream */
@@ -192,8 +201,8 @@ int  crgpu_decode_set_dense_nodes(crgpu_ctx* ctx, crgpu_decode_set* set, uint32_
  * produces for it in that sequence; a stored block is copied out and leaves the models and the context register alone.
  * A block fails — out_size = 0xFFFFFFFF — on a header shorter than 20 bytes, an original size above out_cap or above the
  * set's max_block, or a damaged stream; every later block of its slot then reports 0xFFFFFFFF undecoded, in this call and in
- * later ones, until the slot is reset. CRGPU_E_ARG for a codec other than CRGPU_CODEC_ROP, more sequences than slots, a
- * descending seq_first, a set of another context and a block whose in_size exceeds crgpu_bound(CRGPU_CODEC_ROP, max_block).
+ * later ones, until the slot is reset. CRGPU_E_ARG for a codec other than the set's, more sequences than slots, a
+ * descending seq_first, a set of another context and a block whose in_size exceeds crgpu_bound(the set's codec, max_block).
  * The block sizes are read back once in front of the launch (that check and the order of the sequences need them); the
  * decode itself is one launch that the call only enqueues unless `sync` is non-zero, in which case it returns
  * CRGPU_E_CORRUPT if a block failed, after every other sequence has been decoded. */
