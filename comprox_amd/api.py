@@ -108,6 +108,8 @@ def load_library():
     L.crgpu_encode_blocks_carried.argtypes = [vp, i32, vp, vp, vp, vp, u32, vp, vp, vp]
     L.crgpu_model_set_create.restype = i32
     L.crgpu_model_set_create.argtypes = [vp, u32, u32, ctypes.POINTER(vp)]
+    L.crgpu_model_set_create_codec.restype = i32
+    L.crgpu_model_set_create_codec.argtypes = [vp, i32, u32, u32, ctypes.POINTER(vp)]
     L.crgpu_model_set_destroy.restype = None
     L.crgpu_model_set_destroy.argtypes = [vp]
     L.crgpu_model_set_reset.restype = i32
@@ -356,8 +358,8 @@ class CrGpu:
     def models_create(self) -> "CrModels":
         return CrModels(self)
 
-    def model_set_create(self, nseq: int, max_block: int) -> "CrModelSet":
-        return CrModelSet(self, nseq, max_block)
+    def model_set_create(self, nseq: int, max_block: int, codec: int = CODEC_ROP) -> "CrModelSet":
+        return CrModelSet(self, nseq, max_block, codec)
 
     def encode_sequences(self, sequences, model_set: "CrModelSet", codec: int = CODEC_ROP):
         """sequences: list of lists of bytes-like, sequence s on slot s of the set. Block t of every sequence is coded in one
@@ -629,13 +631,15 @@ class CrModels:
 
 
 class CrModelSet:
-    """`nseq` stores of comprop's PPM models with their undo logs (crgpu_model_set), one slot per sequence of dependent blocks."""
+    """`nseq` stores of one codec's PPM models with their undo logs — and, for comprox and comprolz, the side streams' models —
+    (crgpu_model_set), one slot per sequence of dependent blocks; encode_sequences on it names the same codec."""
 
-    def __init__(self, gpu: CrGpu, nseq: int, max_block: int):
+    def __init__(self, gpu: CrGpu, nseq: int, max_block: int, codec: int = CODEC_ROP):
         self.gpu = gpu
         self.nseq = nseq
+        self.codec = codec
         self.h = ctypes.c_void_p()
-        gpu._check(gpu.lib.crgpu_model_set_create(gpu.h, nseq, max_block, ctypes.byref(self.h)), "crgpu_model_set_create")
+        gpu._check(gpu.lib.crgpu_model_set_create_codec(gpu.h, codec, nseq, max_block, ctypes.byref(self.h)), "crgpu_model_set_create_codec")
 
     def reset(self, which=None):
         """every slot, or the slots listed in `which`, back to the state of reset_models()"""

@@ -28,7 +28,7 @@
 #include "crgpu_lzp2.h"
 #include "crgpu_links2.h"
 #include "crgpu_carry.h"
-#include "crgpu_seq.h"
+#include "crgpu_seq_lz.h"
 #include "crgpu_seqdec.h"
 #include "crgpu_rolz3.h"
 #include "crgpu_rox3.h"
@@ -1739,7 +1739,9 @@ extern "C" int crgpu_encode_blocks_carried_dev(crgpu_ctx* c, int codec, crgpu_mo
 struct crgpu_model_set {
     crgpu_ctx* ctx;
     uint32_t   nseq, max_block, ev_cap;
+    int        codec;                      /* whose models the slots hold: the calls on the set must name it */
     uint8_t*   d_store;                    /* nseq x CR_M_BYTES */
+    uint8_t*   d_keep;                     /* comprox, comprolz: nseq x 2 x CR_SEQ_KEEP_BYTES, the side models and their snapshot (crgpu_seq_lz.h) */
     uint8_t*   d_log;                      /* nseq x log_stride: the undo logs */
     u64        log_stride, off_log3;
     uint32_t*  d_idx;                      /* 3 x nseq words: a call's slot per internal sequence, a reset's list, the order-2 chain counters */
@@ -1752,8 +1754,10 @@ extern "C" int crgpu_model_set_reset(crgpu_ctx* c, crgpu_model_set* m, const uin
     if (!c || !m || m->ctx != c) return CRGPU_E_ARG;
     CR_TRY(c, hipSetDevice(c->device));
     const uint32_t grid = (uint32_t)c->num_cu * 4u;
+    const int rolz = m->codec == CRGPU_CODEC_ROLZ;
     if (!which) {
         crs_launch_fill(c->stream, grid, m->d_store, NULL, m->nseq);
+        if (m->d_keep) crs_launch_side_fill(c->stream, m->d_keep, NULL, m->nseq, rolz);
         CR_TRY(c, hipGetLastError());
         return CRGPU_OK;
     }
@@ -1762,6 +1766,7 @@ extern "C" int crgpu_model_set_reset(crgpu_ctx* c, crgpu_model_set* m, const uin
     for (uint32_t i = 0; i < n; i++) if (which[i] >= m->nseq) { snprintf(c->err, sizeof c->err, "slot %u of a set of %u", which[i], m->nseq); return CRGPU_E_ARG; }
     CR_TRY(c, hipMemcpyAsync(m->d_idx + m->nseq, which, 4u * n, hipMemcpyHostToDevice, c->stream));
     crs_launch_fill(c->stream, grid, m->d_store, m->d_idx + m->nseq, n);
+    if (m->d_keep) crs_launch_side_fill(c->stream, m->d_keep, m->d_idx + m->nseq, n, rolz);
     CR_TRY(c, hipGetLastError());
     CR_TRY(c, hipStreamSynchronize(c->stream));          /* (the list is the caller's memory, and the next reset's list goes to the same place) */
     return CRGPU_OK;
@@ -1771,23 +1776,25 @@ extern "C" void crgpu_model_set_destroy(crgpu_model_set* m) {
     if (!m) return;
     (void)hipSetDevice(m->ctx->device);
     (void)hipStreamSynchronize(m->ctx->stream);
-    (void)hipFree(m->d_store); (void)hipFree(m->d_log); (void)hipFree(m->d_idx); (void)hipFree(m->d_desc);
+    (void)hipFree(m->d_store); (void)hipFree(m->d_keep); (void)hipFree(m->d_log); (void)hipFree(m->d_idx); (void)hipFree(m->d_desc);
     free(m);
 }
 
-extern "C" int crgpu_model_set_create(crgpu_ctx* c, uint32_t nseq, uint32_t max_block, crgpu_model_set** out) {
+extern "C" int crgpu_model_set_create_codec(crgpu_ctx* c, int codec, uint32_t nseq, uint32_t max_block, crgpu_model_set** out) {
     if (!c || !out) return CRGPU_E_ARG;
     *out = NULL;
+    if (codec != CRGPU_CODEC_ROP && codec != CRGPU_CODEC_ROX && codec != CRGPU_CODEC_ROLZ) { snprintf(c->err, sizeof c->err, "codec %d not available", codec); return CRGPU_E_ARG; }
     if (nseq == 0 || nseq > 65535u || max_block > CRGPU_MAX_BLOCK + 1u) { snprintf(c->err, sizeof c->err, "a model set has 1 .. 65535 slots for blocks of up to CRGPU_MAX_BLOCK + 1 bytes"); return CRGPU_E_ARG; }
     CR_TRY(c, hipSetDevice(c->device));
     crgpu_model_set* m = (crgpu_model_set*)calloc(1, sizeof *m);
     if (!m) return CRGPU_E_NOMEM;
-    m->ctx = c; m->nseq = nseq; m->max_block = max_block; m->ev_cap = seq_ev_cap(max_block);
+    m->ctx = c; m->nseq = nseq; m->max_block = max_block; m->ev_cap = seq_ev_cap(max_block); m->codec = codec;
     const u64 n2 = m->ev_cap < 65536u ? m->ev_cap : 65536u, n3 = m->ev_cap < (1u << 22) ? m->ev_cap : (1u << 22);
     m->off_log3 = CR_SEQ_LOG1_BYTES + (u64)CR_SEQ_LOG2_REC * n2;
     m->log_stride = m->off_log3 + 8u * n3;               /* (a multiple of 16: ev_cap is one of 64) */
     if (hipMalloc((void**)&m->d_store, (size_t)(nseq * CR_M_BYTES)) != hipSuccess || hipMalloc((void**)&m->d_log, (size_t)(nseq * m->log_stride)) != hipSuccess ||
-        hipMalloc((void**)&m->d_idx, (size_t)nseq * 12u) != hipSuccess) {
+        hipMalloc((void**)&m->d_idx, (size_t)nseq * 12u) != hipSuccess ||
+        (codec != CRGPU_CODEC_ROP && hipMalloc((void**)&m->d_keep, (size_t)nseq * 2u * CR_SEQ_KEEP_BYTES) != hipSuccess)) {
         (void)hipGetLastError();
         snprintf(c->err, sizeof c->err, "hipMalloc(model set, %u x (%llu + %llu) bytes) failed", nseq, (unsigned long long)CR_M_BYTES, (unsigned long long)m->log_stride);
         crgpu_model_set_destroy(m);
@@ -1797,6 +1804,10 @@ extern "C" int crgpu_model_set_create(crgpu_ctx* c, uint32_t nseq, uint32_t max_
     if (rc != CRGPU_OK) { crgpu_model_set_destroy(m); return rc; }
     *out = m;
     return CRGPU_OK;
+}
+
+extern "C" int crgpu_model_set_create(crgpu_ctx* c, uint32_t nseq, uint32_t max_block, crgpu_model_set** out) {
+    return crgpu_model_set_create_codec(c, CRGPU_CODEC_ROP, nseq, max_block, out);
 }
 
 /* the events of the launch's blocks -> triples: the sorts of crgpu.hip on the sub-batch, then one launch each of the
@@ -1878,6 +1889,89 @@ static int seq_step(crgpu_ctx* c, CrBatch B, const CrArenaLayout& LY, const CrSe
     return CRGPU_OK;
 }
 
+/* the same step of a comprox or comprolz set (crgpu_seq_lz.h): the codec's match pre-pass as launch() runs it, the token loops
+ * on the slots' registers and side models (`keep`), the shared chain stages, the codec's range coder. Every block that came
+ * out stored (roxmain/cr-coder.c:273-275, rolzmain/cr-coder.c:231-233: no size is exempt) goes back through the undo log and
+ * the side models' snapshot to the token where lzencode gave up. A stored block has n + header bytes, but so may a coded one:
+ * only then are the coded flags read (d_flag: one word per active block) */
+static int seq_step_lz(crgpu_ctx* c, int codec, CrBatch B, const CrArenaLayout& LY, const CrSeq& Q, uint8_t* keep, uint32_t* d_flag,
+                       const uint32_t* h_n, uint32_t* h_got, uint32_t grid) {
+    const uint32_t na = B.nblocks;
+    const int rolz = codec == CRGPU_CODEC_ROLZ;
+    uint32_t maxn = 0;
+    for (uint32_t j = 0; j < na; j++) if (h_n[j] > maxn) maxn = h_n[j];
+    CR_TRY(c, hipMemsetAsync(c->ticket, 0, 128, c->stream));
+    CR_TRY(c, hipMemsetAsync(B.pre_done, 0, na, c->stream));
+    CR_CARRY_RC(carry_group_open(c));
+    B.lzp_lds = 0;
+    const uint32_t lg = (uint32_t)c->num_cu < grid ? (uint32_t)c->num_cu : grid;
+    if (rolz) {
+        if (!c->lzp_tables_only) {
+            if (!c->rolz_lds_ready) {
+                CR_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_rolz_match_lds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)CR_LZ2_LDS_BYTES_FOR(CR_ROLZ3_THREADS / 64u)));
+                c->rolz_lds_ready = 1;
+            }
+            B.lzp_lds = 1;
+            CR_CARRY_STAGE("k_rolz_match_lds", hipLaunchKernelGGL(k_rolz_match_lds, dim3(lg), dim3(CR_ROLZ3_THREADS), CR_LZ2_LDS_BYTES_FOR(CR_ROLZ3_THREADS / 64u), c->stream, B, LY));
+            if (maxn > CR_LZ2_MAXN) {
+                if (!c->rolz64_ready) {
+                    CR_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_rolz_rings_lds64), hipFuncAttributeMaxDynamicSharedMemorySize, (int)CR_LZ3_LDS_BYTES));
+                    c->rolz64_ready = 1;
+                }
+                CR_CARRY_STAGE("k_rolz_rings_lds64", hipLaunchKernelGGL(k_rolz_rings_lds64, dim3(lg), dim3(CR_LZ2_THREADS), CR_LZ3_LDS_BYTES, c->stream, B, LY));
+            }
+        }
+        CR_CARRY_STAGE("k_rolz_match", hipLaunchKernelGGL(k_rolz_match, dim3(grid), dim3(256), 0, c->stream, B, LY));
+    } else {
+        if (!c->lzp_tables_only) {
+            if (!c->rox_lds_ready) {
+                CR_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_rox_links_lds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)CR_LZ2_LDS_BYTES));
+                c->rox_lds_ready = 1;
+            }
+            B.lzp_lds = 1;
+            CR_CARRY_STAGE("k_rox_links_lds", hipLaunchKernelGGL(k_rox_links_lds, dim3(lg), dim3(CR_LZ2_THREADS), CR_LZ2_LDS_BYTES, c->stream, B, LY));
+            if (maxn > CR_LZ2_MAXN) {
+                if (!c->rox64_ready) {
+                    CR_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_rox_links_lds64), hipFuncAttributeMaxDynamicSharedMemorySize, (int)CR_LZ3_LDS_BYTES));
+                    c->rox64_ready = 1;
+                }
+                CR_CARRY_STAGE("k_rox_links_lds64", hipLaunchKernelGGL(k_rox_links_lds64, dim3(lg), dim3(CR_LZ2_THREADS), CR_LZ3_LDS_BYTES, c->stream, B, LY));
+            }
+        }
+        CR_CARRY_STAGE("k_rox_match", hipLaunchKernelGGL(k_rox_match, dim3(grid), dim3(256), 0, c->stream, B, LY));
+    }
+    CR_CARRY_STAGE(rolz ? "k_seq_rolz_events" : "k_seq_rox_events", crs_launch_lz_events(c->stream, rolz, B, LY, Q, keep));
+    CR_CARRY_RC(seq_chain_stages(c, B, LY, Q, maxn, grid, 1));
+    if (rolz) CR_CARRY_STAGE("k_rolz_rc", hipLaunchKernelGGL(k_rolz_rc, CR_G(k_rolz_rc, CRGPU_WAVE, 0), dim3(CRGPU_WAVE), 0, c->stream, B, LY));
+    else CR_CARRY_STAGE("k_rox_rc", hipLaunchKernelGGL(k_rox_rc, CR_G(k_rox_rc, CRGPU_WAVE, 0), dim3(CRGPU_WAVE), 0, c->stream, B, LY));
+    CR_CARRY_RC(carry_group_close(c));
+    CR_TRY(c, hipMemcpyAsync(h_got, B.out_size, 4u * na, hipMemcpyDeviceToHost, c->stream));
+    CR_TRY(c, hipStreamSynchronize(c->stream));
+    const uint32_t header = rolz ? 16u : 32u;
+    uint32_t maybe = 0;
+    for (uint32_t j = 0; j < na; j++) if (h_n[j] != 0u && h_got[j] == h_n[j] + header) maybe++;
+    if (maybe == 0) return CRGPU_OK;
+    crs_launch_lz_stored(c->stream, rolz, B, d_flag);
+    CR_TRY(c, hipGetLastError());
+    CR_TRY(c, hipMemcpyAsync(h_got, d_flag, 4u * na, hipMemcpyDeviceToHost, c->stream));
+    CR_TRY(c, hipStreamSynchronize(c->stream));
+    for (uint32_t j = 0; j < na; j++) {
+        if (!h_got[j]) continue;
+        CrBatch B1 = B;
+        B1.in_off += j; B1.in_size += j; B1.out_off += j; B1.out_size += j; B1.nblocks = 1;
+        B1.ev += (u64)j * B.ev_stride; B1.pre_done += j;
+        B1.rox += (u64)j * B.rox_stride; B1.side += (u64)j * 3u * LY.side_stride;
+        CrSeq Q1 = Q;
+        Q1.slot += j; Q1.chain_ctr += j;
+        CR_CARRY_RC(carry_group_open(c));
+        CR_CARRY_STAGE("k_seq_undo", crs_launch_undo(c->stream, B1, Q1));
+        CR_CARRY_STAGE("k_seq_lz_abort", crs_launch_lz_abort(c->stream, rolz, B1, LY, Q1, keep));
+        CR_CARRY_RC(seq_chain_stages(c, B1, LY, Q1, h_n[j], 1u, 0));
+        CR_CARRY_RC(carry_group_close(c));
+    }
+    return CRGPU_OK;
+}
+
 /* Sequence s owns blocks seq_first[s] .. seq_first[s + 1] - 1 (seq_first in HOST memory, everything else on the device) and
  * slot s of the set: its first block starts from the slot's state, block i continues block i - 1, the slot keeps what the
  * last block leaves; a sequence without a block leaves its slot alone. Every block's bytes are what the reference's lzencode
@@ -1886,7 +1980,7 @@ extern "C" int crgpu_encode_sequences_carried_dev(crgpu_ctx* c, int codec, crgpu
                                                   const uint32_t* in_size, const uint32_t* seq_first, uint32_t nseq,
                                                   uint8_t* out, const uint64_t* out_off, uint32_t* out_size) {
     if (!c || !m || m->ctx != c || (nseq && !seq_first)) return CRGPU_E_ARG;
-    if (codec != CRGPU_CODEC_ROP) { snprintf(c->err, sizeof c->err, "models are carried for comprop only (codec %d)", codec); return CRGPU_E_ARG; }
+    if (codec != m->codec) { snprintf(c->err, sizeof c->err, "the model set holds the models of codec %d (codec %d)", m->codec, codec); return CRGPU_E_ARG; }
     if (c->persist || c->one_wave_encoder) { snprintf(c->err, sizeof c->err, "carried models run on the kernel pipeline: not on a one-wave context"); return CRGPU_E_ARG; }
     if (nseq > m->nseq) { snprintf(c->err, sizeof c->err, "%u sequences for a set of %u slots", nseq, m->nseq); return CRGPU_E_ARG; }
     for (uint32_t s = 0; s < nseq; s++) if (seq_first[s + 1u] < seq_first[s]) { snprintf(c->err, sizeof c->err, "seq_first descends at sequence %u", s); return CRGPU_E_ARG; }
@@ -1920,7 +2014,8 @@ extern "C" int crgpu_encode_sequences_carried_dev(crgpu_ctx* c, int codec, crgpu
         }
     uint32_t want = (uint32_t)c->num_cu * (uint32_t)c->wg_per_cu;
     if (want > na0) want = na0;
-    rc = ensure_arena(c, CR_AR_ENC, m->max_block, want, CR_USE_LZ2 | CR_USE_LZP | CR_USE_CAND);
+    const int lz = codec != CRGPU_CODEC_ROP;
+    rc = ensure_arena(c, CR_AR_ENC, m->max_block, want, CR_USE_LZ2 | (!lz ? CR_USE_LZP | CR_USE_CAND : codec == CRGPU_CODEC_ROX ? CR_USE_ROX : CR_USE_RHEAD));
     const crgpu_ctx::arena_set* A = &c->arenas[CR_AR_ENC];
     CrBatch B; memset(&B, 0, sizeof B);
     B.in = in; B.out = out;
@@ -1930,12 +2025,20 @@ extern "C" int crgpu_encode_sequences_carried_dev(crgpu_ctx* c, int codec, crgpu
     B.lens_stride = align_up(m->max_block < 1024u ? 1024u : m->max_block, 256);
     /* per-block scratch is one slot per sequence, reused every step */
     if (rc == CRGPU_OK) rc = grow(c, &c->d_ev, &c->d_ev_cap, (size_t)(B.ev_stride * na0));
-    if (rc == CRGPU_OK) rc = grow(c, &c->d_lens, &c->d_lens_cap, (size_t)(B.lens_stride * na0));
+    if (rc == CRGPU_OK && !lz) rc = grow(c, &c->d_lens, &c->d_lens_cap, (size_t)(B.lens_stride * na0));
+    if (lz) {                                                               /* the match tables and the side staging of launch() */
+        B.rox_stride = align_up(((u64)(m->max_block < 1024u ? 1024u : m->max_block) + 64u) * 16u, 1024);
+        B.rox_limit = c->rox_limit;
+        B.flexible = c->flexible ? 1u : 0u;
+        if (rc == CRGPU_OK) rc = grow(c, &c->d_rox, &c->d_rox_cap, (size_t)(B.rox_stride * na0));
+        if (rc == CRGPU_OK) rc = grow(c, &c->d_side, &c->d_side_cap, (size_t)(3u * A->L.side_stride * na0));
+    }
     if (rc == CRGPU_OK) rc = grow(c, &c->d_done, &c->d_done_cap, (size_t)na0 + 16u);
     if (rc == CRGPU_OK) rc = grow(c, &m->d_desc, &m->desc_cap, (size_t)nb * 28u);
     if (rc != CRGPU_OK) { free(h); return rc; }
     c->done_blocks = 0;
     B.ev = c->d_ev; B.lens = c->d_lens; B.pre_done = c->d_done;
+    if (lz) { B.rox = c->d_rox; B.side = c->d_side; }
     u64* const d_in_off = (u64*)m->d_desc, * const d_out_off = d_in_off + nb;
     uint32_t* const d_in_size = (uint32_t*)(d_out_off + nb), * const d_osz = d_in_size + nb, * const d_map = d_osz + nb;
     CrSeq Q;
@@ -1951,7 +2054,8 @@ extern "C" int crgpu_encode_sequences_carried_dev(crgpu_ctx* c, int codec, crgpu
         uint32_t na = 0;
         while (na < nseq && seq_first[h_perm[na] + 1u] - seq_first[h_perm[na]] > t) na++;
         B.in_off = d_in_off + p; B.in_size = d_in_size + p; B.out_off = d_out_off + p; B.out_size = d_osz + p; B.nblocks = na;
-        rc = seq_step(c, B, A->L, Q, h_perm, h_n + p, h_got, na < grid_cap ? na : grid_cap);
+        if (lz) rc = seq_step_lz(c, codec, B, A->L, Q, m->d_keep, m->d_idx + m->nseq, h_n + p, h_got, na < grid_cap ? na : grid_cap);
+        else rc = seq_step(c, B, A->L, Q, h_perm, h_n + p, h_got, na < grid_cap ? na : grid_cap);
         p += na;
     }
     if (rc == CRGPU_OK) {
@@ -2460,7 +2564,7 @@ extern "C" int crgpu_encode_sequences_carried(crgpu_ctx* c, int codec, crgpu_mod
                                               const uint32_t* in_size, const uint32_t* seq_first, uint32_t nseq,
                                               uint8_t* out, const uint64_t* out_off, uint32_t* out_size) {
     if (!c || !m || (nseq && !seq_first)) return CRGPU_E_ARG;
-    if (codec != CRGPU_CODEC_ROP) { snprintf(c->err, sizeof c->err, "models are carried for comprop only (codec %d)", codec); return CRGPU_E_ARG; }
+    if (codec != m->codec) { snprintf(c->err, sizeof c->err, "the model set holds the models of codec %d (codec %d)", m->codec, codec); return CRGPU_E_ARG; }
     for (uint32_t s = 0; s < nseq; s++) if (seq_first[s + 1u] < seq_first[s]) { snprintf(c->err, sizeof c->err, "seq_first descends at sequence %u", s); return CRGPU_E_ARG; }
     if (nseq == 0) return crgpu_encode_sequences_carried_dev(c, codec, m, NULL, NULL, NULL, NULL, 0, NULL, NULL, NULL);   /* (its refusals hold for an empty call too) */
     uint32_t* rel = (uint32_t*)malloc(sizeof(uint32_t) * ((size_t)nseq + 1u));

@@ -191,6 +191,31 @@ CR_DEV void cr_ropc_o2_all(CrEvViews& V, uint8_t* lane_node, uint8_t* o2, uint32
     }
 }
 
+/* the abort point of a block of n bytes that ended stored: the event-by-event coder of cr_code_events run until the token
+ * loop's test fires (`header` = the bytes the block format puts in front of the stream), its bytes into scratch (escB, dead
+ * since the order-1 pass; a step can release a run of held-back bytes, the region is 8 bytes per event slot). Returns the
+ * number of events up to and including that token */
+CR_DEV uint32_t cr_ropc_abort_cut(const CrEvViews& V, uint32_t n, uint32_t nev, uint32_t header) {
+    CrSink out; out.dst = reinterpret_cast<uint8_t*>(V.escB); out.n = 0;
+    CrRc rc; cr_rc_init(rc);
+    CrEvWindow w;
+    cr_evwin_fill(w, V, 0, nev);
+    for (uint32_t i = 0; i < nev; i++) {
+        if (i - w.base >= CRGPU_WAVE) cr_evwin_fill(w, V, i, nev);
+        const uint32_t l = i - w.base;
+        const u64 t = cr_lane_get64(w.trip, l);
+        cr_rc_pin(rc); out.n = cr_uni(out.n);
+        cr_rc_encode(rc, (uint32_t)t & 0xfffffu, (uint32_t)(t >> 40) & 0x3ffu, (uint32_t)(t >> 20) & 0xfffffu, out);
+        if (((uint32_t)(t >> 50) & 3u) == CR_T_ESC) {
+            const u64 t2 = cr_lane_get64(w.trip2, l);
+            cr_rc_pin(rc); out.n = cr_uni(out.n);
+            cr_rc_encode(rc, (uint32_t)t2 & 0xfffffu, (uint32_t)(t2 >> 40) & 0xfffu, (uint32_t)(t2 >> 20) & 0xfffffu, out);
+        }
+        if ((cr_lane_get(w.sym, l) & CR_EV_LAST) && header + out.n >= n) return i + 1u;
+    }
+    return nev;
+}
+
 #ifdef CRGPU_CARRY_TU
 __global__ __launch_bounds__(CR_O2C_THREADS) void k_ropc_o2(CrBatch B, uint8_t* M) {
     __shared__ __attribute__((aligned(16))) uint8_t s_nodes[CR_O2C_THREADS * CR_LN_STRIDE];
@@ -224,9 +249,8 @@ __global__ __launch_bounds__(CR_O1_THREADS) void k_ropc_o1(CrBatch B, uint8_t* M
 
 /* ------------------------------------------------------------------ the abort point */
 
-/* One wave, behind k_rop_rc, for a block that ended stored although it has events: the event-by-event coder of
- * cr_code_events run until the token loop's test fires (cr-coder.c:204-206), its bytes into scratch (escB, dead since the
- * order-1 pass; a step can release a run of held-back bytes, the region is 8 bytes per event slot). The block's event count
+/* One wave, behind k_rop_rc, for a block that ended stored although it has events: cr_ropc_abort_cut finds the token at which
+ * the token loop's test fires (cr-coder.c:204-206). The block's event count
  * becomes the events up to and including that token, and the store's register the context in front of the NEXT token — the
  * token's own updates applied —, which is the next event's context or, behind the last token, what k_ropc_events left. The
  * host has put its copy of the store back before this runs. */
@@ -235,24 +259,7 @@ __global__ __launch_bounds__(CRGPU_WAVE) void k_ropc_abort(CrBatch B, uint8_t* M
     const uint32_t n = B.in_size[0];
     const uint32_t nev = cr_uni(V.ctr[0]);
     if ((cr_uni(V.ctr[3]) & 0x300u) || nev == 0u) return;
-    CrSink out; out.dst = reinterpret_cast<uint8_t*>(V.escB); out.n = 0;
-    CrRc rc; cr_rc_init(rc);
-    CrEvWindow w;
-    cr_evwin_fill(w, V, 0, nev);
-    uint32_t keep = nev;
-    for (uint32_t i = 0; i < nev; i++) {
-        if (i - w.base >= CRGPU_WAVE) cr_evwin_fill(w, V, i, nev);
-        const uint32_t l = i - w.base;
-        const u64 t = cr_lane_get64(w.trip, l);
-        cr_rc_pin(rc); out.n = cr_uni(out.n);
-        cr_rc_encode(rc, (uint32_t)t & 0xfffffu, (uint32_t)(t >> 40) & 0x3ffu, (uint32_t)(t >> 20) & 0xfffffu, out);
-        if (((uint32_t)(t >> 50) & 3u) == CR_T_ESC) {
-            const u64 t2 = cr_lane_get64(w.trip2, l);
-            cr_rc_pin(rc); out.n = cr_uni(out.n);
-            cr_rc_encode(rc, (uint32_t)t2 & 0xfffffu, (uint32_t)(t2 >> 40) & 0xfffu, (uint32_t)(t2 >> 20) & 0xfffffu, out);
-        }
-        if ((cr_lane_get(w.sym, l) & CR_EV_LAST) && CR_ROP_HEADER + out.n >= n) { keep = i + 1u; break; }
-    }
+    const uint32_t keep = cr_ropc_abort_cut(V, n, nev, CR_ROP_HEADER);
     if (cr_lane() == 0) {
         *reinterpret_cast<uint32_t*>(M + CR_M_OFF_CTX) = keep < nev ? V.ev_ctx[keep] : V.ctr[CR_CTR_END_CTX];
         V.ctr[0] = keep;

@@ -18,14 +18,21 @@
 #define CR_ROLZC_CODES 4     /* V.ctr words: number of side-stream codes, bytes of the side stream */
 #define CR_ROLZC_BSIDE 5
 
-CR_DEV void cr_rolz_emit_events(const uint8_t* src, uint32_t n, const CrRolzTables& T, uint8_t* side, CrEvViews& V, CrRoxShared& sh) {
+/* CARRY (crgpu_seq_lz.h): the side models in `sh` are the caller's (no reset), the context register comes from *ctx_io — the
+ * tokens of positions 1..4 have its bytes in front of the block's own — and goes back there as the token loop leaves it, and
+ * the side stream's symbols are listed in token order, length | rank << 8, for the abort point to replay a prefix of */
+template <bool CARRY = false>
+CR_DEV void cr_rolz_emit_events(const uint8_t* src, uint32_t n, const CrRolzTables& T, uint8_t* side, CrEvViews& V, CrRoxShared& sh,
+                                uint32_t* ctx_io = nullptr, uint16_t* list = nullptr) {
     const uint32_t lane = cr_lane();
     if (n == 0) {                                             /* (the one-wave coder's empty stored block) */
         if (lane == 0) { V.ctr[0] = 0; V.ctr[1] = 0; V.ctr[2] = 0; V.ctr[3] = 0x400u; }
         return;
     }
     const uint32_t esc = cr_pick_escape(src, n, sh.hist);
-    cr_rolz_side_reset(sh);
+    uint32_t reg = 0;
+    if constexpr (CARRY) reg = cr_uni(*ctx_io);
+    else cr_rolz_side_reset(sh);
     cr_wave_sync();
     CrSink s_side; s_side.dst = side; s_side.n = 0;
     CrRc rc_side; cr_rc_init(rc_side);
@@ -53,7 +60,10 @@ CR_DEV void cr_rolz_emit_events(const uint8_t* src, uint32_t n, const CrRolzTabl
             c = sl.c;
             /* the context starts empty at position 1 (cr-coder.c:188): below position 5 it holds src[1 .. p-1] only */
             if (p >= 5u) ctx = __builtin_bswap32(sl.ctx);
-            else ctx = (head4 >> (8u * (4u - p))) & ((1u << (8u * (p - 1u))) - 1u);
+            else {
+                ctx = (head4 >> (8u * (4u - p))) & ((1u << (8u * (p - 1u))) - 1u);
+                if constexpr (CARRY) ctx |= reg << (8u * (p - 1u));
+            }
             if (p >= CR_ROLZ_WARM && p + CR_ROLZ_TAIL < n) { rank = sl.rank; len = sl.len; }
         }
         fetch(sl, base + 2u * CRGPU_WAVE);
@@ -82,6 +92,7 @@ CR_DEV void cr_rolz_emit_events(const uint8_t* src, uint32_t n, const CrRolzTabl
         /* the side stream, in token order (cr-coder.c:205-229) */
         for (u64 todo = cr_ballot(coded_match || (start && c == esc)); todo; todo &= todo - 1ull) {
             const uint32_t l = (uint32_t)__builtin_ctzll(todo);
+            if constexpr (CARRY) { if (lane == 0) list[codes] = (uint16_t)((mm >> l) & 1ull ? cr_lane_get(len, l) | (cr_lane_get(rank, l) << 8) : 0u); }
             if ((mm >> l) & 1ull) {
                 cr_side_encode(sh, CR_ROLZ_M_LEN, cr_lane_get(len, l), 4u, rc_side, s_side);
                 cr_side_encode(sh, CR_ROLZ_M_IDX, cr_lane_get(rank, l), 4u, rc_side, s_side);
@@ -101,6 +112,11 @@ CR_DEV void cr_rolz_emit_events(const uint8_t* src, uint32_t n, const CrRolzTabl
     if (lane == 0) {
         V.ctr[0] = nev; V.ctr[1] = 0; V.ctr[2] = 0; V.ctr[3] = esc;
         V.ctr[CR_ROLZC_CODES] = codes; V.ctr[CR_ROLZC_BSIDE] = s_side.n;
+        if constexpr (CARRY) {                                /* byte 0 never enters the context (cr-coder.c:144,227-229) */
+            if (n >= 5u) reg = __builtin_bswap32(*reinterpret_cast<const cr_u32u*>(src + n - 4u));
+            else for (uint32_t i = 1; i < n; i++) reg = (reg << 8) | src[i];
+            *ctx_io = reg;
+        }
     }
 }
 

@@ -30,13 +30,16 @@
  * records token positions and symbols, contexts are gathered 64 tokens at a time. The only memory the decisions wait
  * for is the 256 bytes at the previous distance (matcher_lookup's repeat test, cr-matcher.c:246-251); they are
  * requested as soon as the next token's position is known, ahead of the side coders. */
-CR_DEV void cr_rox_flush_events(const uint8_t* src, uint32_t n, CrEvViews& V, uint32_t nev0, uint32_t count, uint32_t ppos, uint32_t psym) {
+/* CARRY (crgpu_seq_lz.h): `reg` is the model's context register in front of the block — the tokens of positions 0..3 have its
+ * bytes in front of the block's own */
+template <bool CARRY = false>
+CR_DEV void cr_rox_flush_events(const uint8_t* src, uint32_t n, CrEvViews& V, uint32_t nev0, uint32_t count, uint32_t ppos, uint32_t psym, uint32_t reg = 0) {
     const uint32_t lane = cr_lane();
     if (lane < count) {
         uint32_t ctx;
         if (ppos >= 4u) ctx = __builtin_bswap32(*reinterpret_cast<const cr_u32u*>(src + ppos - 4u));
         else {
-            ctx = 0;
+            ctx = CARRY ? reg : 0u;
             for (uint32_t i = 0; i < ppos; i++) ctx = (ctx << 8) | src[i];
         }
         V.ev_ctx[nev0 + lane] = ctx;
@@ -54,9 +57,13 @@ CR_DEV void cr_rox_flush_events(const uint8_t* src, uint32_t n, CrEvViews& V, ui
         if (lane == 0) { if ((w_) == 1) reinterpret_cast<uint16_t*>(CR_ROX_LIST(1))[cnt_] = (uint16_t)(((m_) << 8) | (sym_)); else CR_ROX_LIST(w_)[cnt_] = (uint8_t)(sym_); } \
         cnt_++; } while (0)
 
+/* ctx_io (CARRY): the register comes from there and goes back as the token loop leaves it (every token pushes its bytes) */
+template <bool CARRY = false>
 CR_DEV void cr_rox_emit_events(const uint8_t* src, uint32_t n, const CrRoxTables& T, uint8_t* side, u64 side_stride,
-                               CrEvViews& V, CrRoxShared& sh) {
+                               CrEvViews& V, CrRoxShared& sh, uint32_t* ctx_io = nullptr) {
     const uint32_t lane = cr_lane();
+    uint32_t reg = 0;
+    if constexpr (CARRY) reg = cr_uni(*ctx_io);
     const uint32_t long_min = 10u + (n > 16777216u ? 1u : 0u);           /* cr-coder.c:192 */
     const uint32_t esc = cr_pick_escape(src, n, sh.hist);
     uint32_t c_spos = 0, c_pos = 0, c_len = 0;                           /* list lengths: stream 0 = spos, 1 = pos, 2 = len */
@@ -93,13 +100,13 @@ CR_DEV void cr_rox_emit_events(const uint8_t* src, uint32_t n, const CrRoxTables
             const u64 pm = cr_ballot(plain) >> first_lane;
             const uint32_t run = pm == ~0ull ? 64u - first_lane : (uint32_t)__builtin_ctzll(~pm);
             if (run > 0u) {
-                cr_rox_flush_events(src, n, V, nev0, nev - nev0, ppos, psym);          /* what the token-by-token part has buffered */
+                cr_rox_flush_events<CARRY>(src, n, V, nev0, nev - nev0, ppos, psym, reg);          /* what the token-by-token part has buffered */
                 const bool mine = lane < run;
                 const uint32_t c = mine ? (uint32_t)src[pos + lane] : 0u;
                 const u64 em = cr_ballot(mine && c == esc);
                 if (mine && c == esc) CR_ROX_LIST(2)[c_len + (uint32_t)__builtin_popcountll(em & ((1ull << lane) - 1ull))] = 0;   /* cr-coder.c:264-267 */
                 c_len += (uint32_t)__builtin_popcountll(em); n_len += (uint32_t)__builtin_popcountll(em);
-                cr_rox_flush_events(src, n, V, nev, run, pos + lane, c | CR_EV_LAST);
+                cr_rox_flush_events<CARRY>(src, n, V, nev, run, pos + lane, c | CR_EV_LAST, reg);
                 nev += run; nev0 = nev;
                 pos += run;
                 /* the next token's bytes at the previous distance (the sequential part expects them loaded) */
@@ -162,16 +169,21 @@ CR_DEV void cr_rox_emit_events(const uint8_t* src, uint32_t n, const CrRoxTables
         if (lane == nev - nev0) { ppos = pos; psym = sym | CR_EV_LAST; }
         nev++;
         if (nev - nev0 == CRGPU_WAVE) {
-            cr_rox_flush_events(src, n, V, nev0, CRGPU_WAVE, ppos, psym);
+            cr_rox_flush_events<CARRY>(src, n, V, nev0, CRGPU_WAVE, ppos, psym, reg);
             nev0 = nev;
         }
         pos += len;
     }
-    cr_rox_flush_events(src, n, V, nev0, nev - nev0, ppos, psym);
+    cr_rox_flush_events<CARRY>(src, n, V, nev0, nev - nev0, ppos, psym, reg);
     if (lane == 0) {
         V.ctr[0] = nev; V.ctr[1] = 0; V.ctr[2] = 0; V.ctr[3] = esc;
         V.ctr[CR_ROXC_NSPOS] = n_spos; V.ctr[CR_ROXC_NPOS] = n_pos; V.ctr[CR_ROXC_NLEN] = n_len;
         V.ctr[CR_ROXC_LIST + 0] = c_spos; V.ctr[CR_ROXC_LIST + 1] = c_pos; V.ctr[CR_ROXC_LIST + 2] = c_len;
+        if constexpr (CARRY) {
+            if (n >= 4u) reg = __builtin_bswap32(*reinterpret_cast<const cr_u32u*>(src + n - 4u));
+            else for (uint32_t i = 0; i < n; i++) reg = (reg << 8) | src[i];
+            *ctx_io = reg;
+        }
     }
 }
 

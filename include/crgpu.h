@@ -145,9 +145,19 @@ int crgpu_encode_blocks_carried(crgpu_ctx* ctx, int codec, crgpu_models* m,
  *   65 792 + 280 x min(E, 65 536) + 8 x min(E, 1 << 22) bytes, E = align_up(max(max_block, 1024) + max_block / 64 + 128, 64)
  * — the chain start states a block overwrites, which a block that ends stored goes back to: no second store per sequence
  * and no store-sized copy per block. create leaves every slot in the ppm_model_init state; reset puts the slots
- * which[0 .. n) back there (which == NULL: all of them; `which` is HOST memory). The set belongs to its context. */
+ * which[0 .. n) back there (which == NULL: all of them; `which` is HOST memory). The set belongs to its context.
+ *
+ * A set is made for ONE codec and the calls on it must name that codec. comprox and comprolz keep, beside the PPM model, the
+ * small adaptive models of their side streams between blocks (roxmain/cr-coder.c:55-60: len_model, pos_models[6],
+ * spos_model; rolzmain: len_model, idx_model). A set of theirs holds per slot the same 26 280 192-byte store and undo log and,
+ * in an allocation of its own, 2 x 4 352 = 8 704 bytes more: the side models (u16[8][256] counts and their totals) and the
+ * snapshot of them from in front of the slot's current block, which a block that ends stored goes back to. reset puts them
+ * back to reset_models' state too. Per-block scratch is one slot per sequence, reused every step: 16 x (max(max_block, 1024)
+ * + 64) bytes of match tables (comprolz: ring and link tables) and 3 x (2 x max_block + 256) bytes of side-stream staging,
+ * both rounded up to 1 KiB / 256 bytes. crgpu_model_set_create is crgpu_model_set_create_codec with CRGPU_CODEC_ROP. */
 typedef struct crgpu_model_set crgpu_model_set;
 int  crgpu_model_set_create(crgpu_ctx* ctx, uint32_t nseq, uint32_t max_block, crgpu_model_set** out);
+int  crgpu_model_set_create_codec(crgpu_ctx* ctx, int codec, uint32_t nseq, uint32_t max_block, crgpu_model_set** out);
 void crgpu_model_set_destroy(crgpu_model_set* set);
 int  crgpu_model_set_reset(crgpu_ctx* ctx, crgpu_model_set* set, const uint32_t* which, uint32_t n);
 /* Pointer conventions of crgpu_encode_blocks_dev, except seq_first: HOST memory, nseq + 1 entries, ascending. Sequence s owns
@@ -155,8 +165,11 @@ int  crgpu_model_set_reset(crgpu_ctx* ctx, crgpu_model_set* set, const uint32_t*
  * block starts from the slot's state, block i continues block i - 1, and on return the slot holds the state behind the
  * sequence's last block — so a sequence may be fed in slices over several calls; a slot without a block in a call is not
  * touched. Every block's bytes are what the reference's lzencode writes for it in its sequence; the rules of
- * crgpu_encode_blocks_carried_dev for blocks under 16 bytes and blocks that end stored hold per sequence. CRGPU_E_ARG for a
- * codec other than CRGPU_CODEC_ROP, a one-wave context, a block above the set's max_block, more sequences than slots, a
+ * crgpu_encode_blocks_carried_dev for blocks under 16 bytes and blocks that end stored hold per sequence (comprop). A comprox
+ * or comprolz block ends stored when the header (32 / 16 bytes) and the main stream reach the input's size behind any token;
+ * the models then stay as they stood behind that token, side models included, and no block is too small to move them: one
+ * of up to header bytes is given up at its first token (a comprolz block of 1 byte has no token and comes out coded, one of
+ * 0 bytes leaves its slot alone). CRGPU_E_ARG for a codec other than the set's, a one-wave context, a block above the set's max_block, more sequences than slots, a
  * descending seq_first and a set of another context. The call returns when all blocks are coded. */
 int crgpu_encode_sequences_carried_dev(crgpu_ctx* ctx, int codec, crgpu_model_set* set,
                                        const uint8_t* in, const uint64_t* in_off, const uint32_t* in_size,

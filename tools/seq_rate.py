@@ -1,14 +1,20 @@
 """Many sequences of dependent comprop blocks: one crgpu_encode_sequences_carried_dev call (block t of every sequence in one
 pass of the pipeline, crgpu_seq.h) against crgpu_encode_blocks_carried_dev called once per sequence, in the same process.
 
-  python tools/seq_rate.py [--runs 5] [--out profiles/r10a_seq_rate.txt]
+  python tools/seq_rate.py [--runs 5] [--codec rop|rox|rolz] [--out profiles/r10a_seq_rate.txt]
 
 S sequences of 16 blocks of 64 KiB of corpus.enwik_like text with distinct seeds, S = 1, 16, 128, everything in device memory.
 Wall clock around the call(s) — both entry points return when the blocks are coded —, the median of --runs after one
 warm-up, the two ways alternating; the models are reset in front of every run (inside the clock: a user resets them too) and
 the bytes of the two ways must be equal. Then the new call's kernels by name from the stage log, for every S.
+
+--codec rox / rolz (crgpu_seq_lz.h): the path the call replaces is the lzencode shim with carried models — reset_models() and one
+lzencode per block on the one-wave coder —, which codes ONE sequence at a time: it is timed on sequence 0 alone, its bytes must
+equal the call's for that sequence, and its rate stands for any S. The blocks that came out stored are counted: the abort path
+ran once for each.
 """
 import argparse
+import ctypes
 import os
 import statistics
 import sys
@@ -37,11 +43,11 @@ def sequence_text(s):
 class Job:
     """S sequences on the device: the flat block arrays of both entry points"""
 
-    def __init__(self, nseq):
-        self.nseq, nb = nseq, nseq * PER_SEQ
+    def __init__(self, nseq, codec=api.CODEC_ROP):
+        self.nseq, nb, self.codec = nseq, nseq * PER_SEQ, codec
         text = np.concatenate([sequence_text(s) for s in range(nseq)])
         dev = lambda a: torch.from_numpy(a.view(np.uint8).copy()).cuda()        # noqa: E731
-        self.cap = api.bound(api.CODEC_ROP, BLOCK)
+        self.cap = api.bound(codec, BLOCK)
         self.keep = [dev(np.append(text, np.uint8(0))), dev(np.arange(nb, dtype=np.uint64) * BLOCK), dev(np.full(nb, BLOCK, dtype=np.uint32)),
                      dev(np.arange(nb, dtype=np.uint64) * self.cap)]
         self.out = torch.zeros(nb * self.cap, dtype=torch.uint8, device="cuda")
@@ -59,7 +65,8 @@ class Job:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         ms.reset()
-        gpu.encode_sequences_carried_dev(ms, self.d_in, self.d_io, self.d_sz, self.seq_first, self.out.data_ptr(), self.d_oo, self.osz.data_ptr())
+        gpu.encode_sequences_carried_dev(ms, self.d_in, self.d_io, self.d_sz, self.seq_first, self.out.data_ptr(), self.d_oo, self.osz.data_ptr(),
+                                         codec=self.codec)
         return time.perf_counter() - t0
 
     def one_by_one(self, gpu, models):
@@ -74,11 +81,74 @@ class Job:
         return time.perf_counter() - t0
 
 
+def shim_sequence(lib, codec, blocks):
+    """reset_models() + one lzencode per block on the library's model-carrying shim: (seconds, coded blocks)"""
+    lib.crgpu_shim_config(codec, 0)
+    ibs = []
+    for b in blocks:
+        ib = api.DataBlock()
+        lib.data_block_resize(ctypes.byref(ib), len(b))
+        ctypes.memmove(ib.m_data, b, len(b))
+        ibs.append(ib)
+    t0 = time.perf_counter()
+    lib.reset_models()
+    outs = []
+    for ib in ibs:
+        ob = api.DataBlock()
+        lib.lzencode(ctypes.byref(ib), ctypes.byref(ob), 0)
+        outs.append(ob)
+    dt = time.perf_counter() - t0
+    data = [ctypes.string_at(ob.m_data, ob.m_size) for ob in outs]
+    for d in ibs + outs:
+        lib.data_block_destroy(ctypes.byref(d))
+    return dt, data
+
+
+def main_lz(args, codec):
+    lib = comprox_amd.load_library()
+    blocks0 = [sequence_text(0)[i * BLOCK:(i + 1) * BLOCK].tobytes() for i in range(PER_SEQ)]
+    shim = [shim_sequence(lib, codec, blocks0) for _ in range(args.runs + 1)][1:]
+    shim_t, one = statistics.median(t for t, _ in shim), PER_SEQ * BLOCK
+    lines = [f"lzencode shim, carried models, reset_models() + {PER_SEQ} calls, one sequence: {shim_t * 1e3:9.1f} ms median of {args.runs} "
+             f"(min {min(t for t, _ in shim) * 1e3:.1f}, max {max(t for t, _ in shim) * 1e3:.1f}) = {one / shim_t / 1e6:8.2f} MB/s"]
+    gpu, step = comprox_amd.CrGpu(0), {}
+    for nseq in SEQS:
+        job, ms = Job(nseq, codec), gpu.model_set_create(nseq, BLOCK, codec)
+        job.lockstep(gpu, ms)
+        coded = job.coded()
+        assert coded[:PER_SEQ] == shim[0][1], "the call and the shim wrote different bytes for sequence 0"
+        stored = sum(1 for e in coded if e[0 if codec == api.CODEC_ROX else 1] == 0)
+        t = [job.lockstep(gpu, ms) for _ in range(args.runs)]
+        med = statistics.median(t)
+        step[nseq] = med * 1e3 / PER_SEQ
+        lines.append(f"S = {nseq:3d} x {PER_SEQ} blocks of 64 KiB: crgpu_encode_sequences_carried_dev, one call {med * 1e3:9.1f} ms median of {args.runs} "
+                     f"(min {min(t) * 1e3:.1f}, max {max(t) * 1e3:.1f}) = {job.bytes / med / 1e6:8.2f} MB/s, {step[nseq]:6.2f} ms per step, "
+                     f"{job.bytes / med / (one / shim_t):.1f}x the shim's rate; {sum(map(len, coded))} coded bytes, sequence 0 equal to the shim's, "
+                     f"{stored} of {len(coded)} blocks stored (abort path runs)")
+        gpu.stage_log(True)
+        job.lockstep(gpu, ms)
+        for k, (msec, cnt) in sorted(gpu.stage_log_read().items(), key=lambda kv: -kv[1][0]):
+            lines.append(f"    {k:20s} {msec:9.2f} ms in {cnt} launches")
+        gpu.stage_log(False)
+        ms.close()
+    lines.append("step time: " + ", ".join(f"S = {k}: {v:.2f} ms" for k, v in step.items()))
+    gpu.close()
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--codec", choices=("rop", "rox", "rolz"), default="rop")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.codec != "rop":
+        text = "\n".join(main_lz(args, api.CODEC_ROX if args.codec == "rox" else api.CODEC_ROLZ))
+        print(text)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text + "\n")
+        return
     gpu = comprox_amd.CrGpu(0)
     models = gpu.models_create()
     lines, rate = [], {}
