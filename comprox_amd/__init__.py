@@ -6,4 +6,4 @@ ABI used by the tests and bench.py. There is no CPU fallback: without the compil
 without a gfx950 device every call raises.
 """
 from . import api  # noqa: F401
-from .api import CrGpu, CrDict, CrModels, CrMulti, CrGpuError, load_library, CODEC_ROP, CODEC_ROX, CODEC_ROLZ, bound  # noqa: F401
+from .api import CrGpu, CrDict, CrDictSet, CrModels, CrMulti, CrGpuError, load_library, CODEC_ROP, CODEC_ROX, CODEC_ROLZ, bound  # noqa: F401

@@ -148,6 +148,22 @@ def load_library():
     L.crgpu_dict_encode_blocks_dev.argtypes = [vp, vp, vp, vp, vp, u32, u32, vp, vp, vp, i32]
     L.crgpu_dict_decode_blocks_dev.restype = i32
     L.crgpu_dict_decode_blocks_dev.argtypes = [vp, vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, i32]
+    L.crgpu_dict_set_create.restype = i32
+    L.crgpu_dict_set_create.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), u32, i32, ctypes.POINTER(vp)]
+    L.crgpu_dict_set_destroy.restype = None
+    L.crgpu_dict_set_destroy.argtypes = [vp]
+    L.crgpu_dict_set_words.restype = i32
+    L.crgpu_dict_set_words.argtypes = [vp, u32]
+    L.crgpu_dict_set_nodes.restype = i32
+    L.crgpu_dict_set_nodes.argtypes = [vp, u32]
+    L.crgpu_dict_encode_sequences.restype = i32
+    L.crgpu_dict_encode_sequences.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp, vp]
+    L.crgpu_dict_decode_sequences.restype = i32
+    L.crgpu_dict_decode_sequences.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
+    L.crgpu_dict_encode_sequences_dev.restype = i32
+    L.crgpu_dict_encode_sequences_dev.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, vp, vp, vp, i32]
+    L.crgpu_dict_decode_sequences_dev.restype = i32
+    L.crgpu_dict_decode_sequences_dev.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, i32]
     L.crgpu_dicpick_dev.restype = i32
     L.crgpu_dicpick_dev.argtypes = [vp, vp, ctypes.c_uint64, ctypes.POINTER(DataBlock), ctypes.POINTER(DicpickInfo)]
     L.crgpu_dicpick.restype = i32
@@ -452,6 +468,10 @@ class CrGpu:
     # ---- static-dictionary stage ----------------------------------------------------
     def dict_create(self, text: bytes) -> "CrDict":
         return CrDict(self, text)
+
+    def dict_set_create(self, texts, with_trie: bool = True) -> "CrDictSet":
+        """One dictionary per sequence of blocks, all made in one call, their tries built on the device."""
+        return CrDictSet(self, texts, with_trie)
 
     def _dicpick(self, fn, what, src, n):
         db, info = DataBlock(), DicpickInfo()
@@ -763,3 +783,87 @@ class CrDict:
                                             _ptr(out), _ptr(out_off), _ptr(caps), _ptr(out_size))
         g._check(rc, "crgpu_dict_decode_blocks", allow=() if strict else (-4,))
         return [None if int(s) == 0xFFFFFFFF else out[int(o):int(o) + int(s)].tobytes() for o, s in zip(out_off, out_size)]
+
+
+class CrDictSet:
+    """crgpu_dict_set: one static dictionary per sequence of blocks, made in one call with the tries built on the device; the
+    stage calls code all sequences in one launch per kernel. with_trie=False: words only (decodes, refuses to encode)."""
+
+    def __init__(self, gpu: CrGpu, texts, with_trie: bool = True):
+        self.gpu = gpu
+        texts = [bytes(t) if bytes(t).endswith(b"\0") else bytes(t) + b"\0" for t in texts]
+        self.ndict = len(texts)
+        arr = (ctypes.c_char_p * max(1, self.ndict))(*texts)
+        h = ctypes.c_void_p()
+        gpu._check(gpu.lib.crgpu_dict_set_create(gpu.h, arr, self.ndict, int(with_trie), ctypes.byref(h)), "crgpu_dict_set_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None) and self.gpu.h:
+            self.gpu.lib.crgpu_dict_set_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def words(self, i: int) -> int:
+        """dictionary_load's return value for dictionary i"""
+        n = int(self.gpu.lib.crgpu_dict_set_words(self.h, i))
+        self.gpu._check(min(n, 0), "crgpu_dict_set_words")
+        return n
+
+    def nodes(self, i: int) -> int:
+        """trie nodes of dictionary i, the root included; 0 for a set without tries"""
+        n = int(self.gpu.lib.crgpu_dict_set_nodes(self.h, i))
+        self.gpu._check(min(n, 0), "crgpu_dict_set_nodes")
+        return n
+
+    @staticmethod
+    def _pack(seqs):
+        blocks = [bytes(b) for s in seqs for b in s]
+        seq_first = np.zeros(len(seqs) + 1, dtype=np.uint32)
+        seq_first[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
+        sizes = np.array([len(b) for b in blocks], dtype=np.uint32)
+        in_off = np.zeros(len(blocks), dtype=np.uint64)
+        in_off[1:] = np.cumsum(sizes[:-1], dtype=np.uint64)
+        src = np.frombuffer(b"".join(blocks) or b"\0", dtype=np.uint8)
+        return seq_first, sizes, in_off, src
+
+    @staticmethod
+    def _unpack(seqs, out, out_off, out_size):
+        flat = [None if int(s) == 0xFFFFFFFF else out[int(o):int(o) + int(s)].tobytes() for o, s in zip(out_off, out_size)]
+        it = iter(flat)
+        return [[next(it) for _ in s] for s in seqs]
+
+    def encode_sequences(self, seqs):
+        """seqs[s]: the blocks of sequence s -> dictionary_encode of each with dictionary s, in the same shape."""
+        seq_first, sizes, in_off, src = self._pack(seqs)
+        nb = len(sizes)
+        caps = sizes.astype(np.uint64) + 1
+        out_off = np.zeros(nb, dtype=np.uint64)
+        out_off[1:] = np.cumsum(caps[:-1], dtype=np.uint64)
+        out = np.zeros(max(1, int(caps.sum())), dtype=np.uint8)
+        out_size = np.zeros(max(1, nb), dtype=np.uint32)
+        g = self.gpu
+        g._check(g.lib.crgpu_dict_encode_sequences(g.h, self.h, _ptr(src), _ptr(in_off), _ptr(sizes), _ptr(seq_first), len(seqs),
+                                                   _ptr(out), _ptr(out_off), _ptr(out_size)), "crgpu_dict_encode_sequences")
+        return self._unpack(seqs, out, out_off, out_size[:nb])
+
+    def decode_sequences(self, seqs, caps, strict=True):
+        """seqs[s]: the coded blocks of sequence s, caps[s]: the room of each -> dictionary_decode with dictionary s (None for a
+        block that could not be decoded, unless strict)."""
+        seq_first, sizes, in_off, src = self._pack(seqs)
+        nb = len(sizes)
+        caps = np.array([c for s in caps for c in s], dtype=np.uint32)
+        out_off = np.zeros(nb, dtype=np.uint64)
+        out_off[1:] = np.cumsum(caps[:-1].astype(np.uint64), dtype=np.uint64)
+        out = np.zeros(max(1, int(caps.astype(np.uint64).sum())), dtype=np.uint8)
+        out_size = np.zeros(max(1, nb), dtype=np.uint32)
+        g = self.gpu
+        rc = g.lib.crgpu_dict_decode_sequences(g.h, self.h, _ptr(src), _ptr(in_off), _ptr(sizes), _ptr(seq_first), len(seqs),
+                                               _ptr(out), _ptr(out_off), _ptr(caps), _ptr(out_size))
+        g._check(rc, "crgpu_dict_decode_sequences", allow=() if strict else (-4,))
+        return self._unpack(seqs, out, out_off, out_size[:nb])

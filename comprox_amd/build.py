@@ -19,10 +19,11 @@ EXTRA_LIBS = ["-lpthread", "-ldl"]
 # per-source compile flags: the carried-model kernels are built without the packed fp32 forms (they are integer code in any case)
 _NO_PK_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SOURCE_FLAGS = {"crgpu_carry.hip": _NO_PK_FP32, "crgpu_seq.hip": _NO_PK_FP32}
-# HIP: kernels + C-ABI; the carried-model kernels; the same for many sequences in lockstep; the decoder of many sequences; the multi-GPU block loop
-SOURCES = ["crgpu.hip", "crgpu_carry.hip", "crgpu_seq.hip", "crgpu_seqdec.hip", "crgpu_multi.hip"]
+# HIP: kernels + C-ABI; the carried-model kernels; the same for many sequences in lockstep; the decoder of many sequences; the
+# tries of a dictionary set; the multi-GPU block loop
+SOURCES = ["crgpu.hip", "crgpu_carry.hip", "crgpu_seq.hip", "crgpu_seqdec.hip", "crgpu_dictset.hip", "crgpu_multi.hip"]
 HOST_C = ["crhost_dict.c", "crhost_filter.c"]         # plain C host passes (gcc), linked into the same library
-HEADERS = ["crgpu_device.h", "crgpu_wave.h", "crgpu_ppm.h", "crgpu_lzp.h", "crgpu_lzp2.h", "crgpu_links2.h", "crgpu_carry.h", "crgpu_seq.h", "crgpu_seq_lz.h", "crgpu_seqdec.h", "crgpu_rolz3.h", "crgpu_rox3.h", "crgpu_rop.h", "crgpu_dict.h", "crgpu_rox.h", "crgpu_rolz.h", "crgpu_rop2.h", "crgpu_dec.h", "crgpu_rop5.h", "crgpu_rox5.h", "crgpu_rolz5.h", "crgpu_rox2.h", "crgpu_rolz2.h", "crgpu_dicpick.h", "crgpu_filter.h"]
+HEADERS = ["crgpu_device.h", "crgpu_wave.h", "crgpu_ppm.h", "crgpu_lzp.h", "crgpu_lzp2.h", "crgpu_links2.h", "crgpu_carry.h", "crgpu_seq.h", "crgpu_seq_lz.h", "crgpu_seqdec.h", "crgpu_rolz3.h", "crgpu_rox3.h", "crgpu_rop.h", "crgpu_dict.h", "crgpu_dictset.h", "crgpu_rox.h", "crgpu_rolz.h", "crgpu_rop2.h", "crgpu_dec.h", "crgpu_rop5.h", "crgpu_rox5.h", "crgpu_rolz5.h", "crgpu_rox2.h", "crgpu_rolz2.h", "crgpu_dicpick.h", "crgpu_filter.h"]
 
 
 def _stale() -> bool:

@@ -17,6 +17,7 @@
 #include "../../include/crgpu.h"
 #include "crgpu_rop.h"
 #include "crgpu_dict.h"
+#include "crgpu_dictset.h"
 #include "crgpu_rox.h"
 #include "crgpu_rolz.h"
 #include "crgpu_rop2.h"
@@ -732,7 +733,15 @@ struct CrDictBatch {
     uint32_t*       match;        /* encode: what the trie says about every position, block b at match + b * match_stride */
     u64             match_stride; /* in entries */
     uint32_t        max_block;
+    const CrDict*   set;          /* SET kernels: the dictionaries of a crgpu_dict_set ... */
+    const uint32_t* block_dict;   /* ... and which of them block b is coded with (its sequence) */
 };
+/* the dictionary of block b: the call's one dictionary, or with SET the one of the block's sequence */
+template <bool SET>
+CR_DEV decltype(auto) cr_dict_of(const CrDictBatch& DB, uint32_t b) {
+    if constexpr (SET) return CrDict(DB.set[DB.block_dict[b]]);
+    else return (DB.dict);                                          /* the kernel's own argument, by reference as before */
+}
 
 /* the trie's answer for every position of every block (crgpu_dict.h). Only about one position in six can start a word,
  * and a wave is as slow as its longest walk, so a workgroup first collects the word starts of its 2 048 positions in LDS
@@ -741,6 +750,7 @@ struct CrDictBatch {
 #ifndef CR_DM_CHUNK
 #define CR_DM_CHUNK 2048u
 #endif
+template <bool SET = false>
 __global__ __launch_bounds__(256) void k_dict_match(CrBatch B, CrDictBatch DB) {
     __shared__ uint32_t s_start[CR_DM_CHUNK];
     __shared__ uint32_t s_count;
@@ -748,6 +758,7 @@ __global__ __launch_bounds__(256) void k_dict_match(CrBatch B, CrDictBatch DB) {
     const uint32_t n = B.in_size[b];
     const uint32_t base = blockIdx.y * CR_DM_CHUNK;
     if (n > DB.max_block || base >= n) return;
+    const CrDict& D = cr_dict_of<SET>(DB, b);
     const uint8_t* src = B.in + B.in_off[b];
     uint32_t* m = DB.match + (u64)b * DB.match_stride;
     const uint32_t end = base + CR_DM_CHUNK < n ? base + CR_DM_CHUNK : n;
@@ -775,10 +786,11 @@ __global__ __launch_bounds__(256) void k_dict_match(CrBatch B, CrDictBatch DB) {
         const uint32_t p = s_start[i];
         const uint32_t q = p / CR_DIC_PIECE, first = q * CR_DIC_PIECE;
         const uint32_t psize = n - first < CR_DIC_PIECE ? n - first : CR_DIC_PIECE;
-        m[p] = cr_dict_match_at(DB.dict, src + first, psize, p - first);
+        m[p] = cr_dict_match_at(D, src + first, psize, p - first);
     }
 }
 
+template <bool SET = false>
 __global__ __launch_bounds__(CRGPU_WAVE) void k_dict_encode(CrBatch B, CrDictBatch DB) {
     __shared__ CrDictShared sh;
     uint8_t* tmp = DB.tmp + (u64)blockIdx.x * DB.tmp_stride;
@@ -789,12 +801,13 @@ __global__ __launch_bounds__(CRGPU_WAVE) void k_dict_encode(CrBatch B, CrDictBat
         if (b >= B.nblocks) break;
         const uint32_t n = B.in_size[b];
         uint32_t r = n > DB.max_block ? 0xFFFFFFFFu
-                   : cr_dict_encode_block(DB.dict, sh, B.in + B.in_off[b], n, DB.match + (u64)b * DB.match_stride, B.out + B.out_off[b], tmp);
+                   : cr_dict_encode_block(cr_dict_of<SET>(DB, b), sh, B.in + B.in_off[b], n, DB.match + (u64)b * DB.match_stride, B.out + B.out_off[b], tmp);
         if (threadIdx.x == 0) B.out_size[b] = r;
         cr_wave_sync();
     }
 }
 
+template <bool SET = false>
 __global__ __launch_bounds__(CRGPU_WAVE) void k_dict_decode(CrBatch B, CrDictBatch DB) {
     __shared__ CrDictShared sh;
     __shared__ __attribute__((aligned(16))) uint8_t s_ring[CR_DD_RING];
@@ -803,7 +816,7 @@ __global__ __launch_bounds__(CRGPU_WAVE) void k_dict_decode(CrBatch B, CrDictBat
         if (threadIdx.x == 0) t = atomicAdd(B.ticket, 1u);
         const uint32_t b = cr_uni(t);
         if (b >= B.nblocks) break;
-        uint32_t r = cr_dict_decode_block(DB.dict, sh, B.in + B.in_off[b], B.in_size[b], B.out + B.out_off[b], B.out_cap[b], s_ring);
+        uint32_t r = cr_dict_decode_block(cr_dict_of<SET>(DB, b), sh, B.in + B.in_off[b], B.in_size[b], B.out + B.out_off[b], B.out_cap[b], s_ring);
         if (threadIdx.x == 0) B.out_size[b] = r;
         cr_wave_sync();
     }
@@ -2229,17 +2242,14 @@ struct crgpu_dict {
     uint8_t*   d_match; size_t match_cap;
 };
 
-/* dictionary_load(text, 1) — cr-diccode.c:76-118 — then flattened for the device */
-extern "C" int crgpu_dict_create(crgpu_ctx* c, const char* text, crgpu_dict** out) {
-    if (!c || !text || !out) return CRGPU_E_ARG;
-    *out = NULL;
-    const uint32_t MAXW = 25000u;                                  /* cr-diccode.h:39 */
-    uint8_t* words = (uint8_t*)calloc(MAXW + 1, CR_DIC_WORD_STRIDE);
-    uint8_t* wlen = (uint8_t*)calloc(MAXW + 1, 1);
-    if (!words || !wlen) { free(words); free(wlen); return CRGPU_E_NOMEM; }
+/* the line parse of dictionary_load — cr-diccode.c:76-106 — into zero-filled words[MAXW + 1][24] / wlen[MAXW + 1] (a last line
+ * without its '\n' leaves its bytes in slot *nw and is no word). CRGPU_E_ARG: text behind the 25 000th line. */
+static const uint32_t CR_DIC_MAXW = 25000u;                        /* cr-diccode.h:39 */
+static int dict_parse(const char* text, uint8_t* words, uint8_t* wlen, uint32_t* nwords) {
+    const uint32_t MAXW = CR_DIC_MAXW;
     uint32_t nw = 0, p = 0;
     for (size_t i = 0; text[i]; i++) {
-        if (nw >= MAXW) { free(words); free(wlen); return CRGPU_E_ARG; }
+        if (nw >= MAXW) return CRGPU_E_ARG;
         uint8_t* w = words + (size_t)nw * CR_DIC_WORD_STRIDE;
         if (text[i] == '\n') {
             if (p > 0 && p + 2 <= CR_DIC_WORD_STRIDE && ((uint32_t)((w[p - 1] | 0x20u) - 'a') < 26u)) { w[p++] = ' '; }   /* words ending in a letter own their space */
@@ -2250,6 +2260,20 @@ extern "C" int crgpu_dict_create(crgpu_ctx* c, const char* text, crgpu_dict** ou
             w[p++] = (uint8_t)text[i];
         }
     }
+    *nwords = nw;
+    return CRGPU_OK;
+}
+
+/* dictionary_load(text, 1) — cr-diccode.c:76-118 — then flattened for the device */
+extern "C" int crgpu_dict_create(crgpu_ctx* c, const char* text, crgpu_dict** out) {
+    if (!c || !text || !out) return CRGPU_E_ARG;
+    *out = NULL;
+    const uint32_t MAXW = CR_DIC_MAXW;
+    uint8_t* words = (uint8_t*)calloc(MAXW + 1, CR_DIC_WORD_STRIDE);
+    uint8_t* wlen = (uint8_t*)calloc(MAXW + 1, 1);
+    if (!words || !wlen) { free(words); free(wlen); return CRGPU_E_NOMEM; }
+    uint32_t nw = 0;
+    if (dict_parse(text, words, wlen, &nw) != CRGPU_OK) { free(words); free(wlen); return CRGPU_E_ARG; }
     /* trie: node 0 is the root; a node that gains a child stops being terminal (cr-diccode.c:47-70) */
     uint32_t cap = 4096, nn = 1, tw = 0;
     uint32_t* next = (uint32_t*)calloc((size_t)cap * 128, 4);
@@ -2352,15 +2376,15 @@ static int dict_launch(crgpu_ctx* c, crgpu_dict* d, int decode, CrBatch& B, uint
     CR_TRY(c, hipEventRecord(c->ev_stage[0], c->stream));
     c->n_stages = 0;
     if (decode) {
-        hipLaunchKernelGGL(k_dict_decode, CR_G(k_dict_decode, CRGPU_WAVE, 0), dim3(CRGPU_WAVE), 0, c->stream, B, DB);
+        hipLaunchKernelGGL(k_dict_decode<>, CR_G(k_dict_decode<>, CRGPU_WAVE, 0), dim3(CRGPU_WAVE), 0, c->stream, B, DB);
         c->stage_name[c->n_stages++] = "k_dict_decode";
     } else {
         const uint32_t chunks = (max_block + CR_DM_CHUNK - 1u) / CR_DM_CHUNK;
-        hipLaunchKernelGGL(k_dict_match, dim3(B.nblocks, chunks ? chunks : 1u), dim3(256), 0, c->stream, B, DB);
+        hipLaunchKernelGGL(k_dict_match<>, dim3(B.nblocks, chunks ? chunks : 1u), dim3(256), 0, c->stream, B, DB);
         CR_TRY(c, hipGetLastError());
         c->stage_name[c->n_stages++] = "k_dict_match";
         CR_TRY(c, hipEventRecord(c->ev_stage[c->n_stages], c->stream));
-        hipLaunchKernelGGL(k_dict_encode, CR_G(k_dict_encode, CRGPU_WAVE, 0), dim3(CRGPU_WAVE), 0, c->stream, B, DB);
+        hipLaunchKernelGGL(k_dict_encode<>, CR_G(k_dict_encode<>, CRGPU_WAVE, 0), dim3(CRGPU_WAVE), 0, c->stream, B, DB);
         c->stage_name[c->n_stages++] = "k_dict_encode";
     }
     CR_TRY(c, hipGetLastError());
@@ -2462,7 +2486,8 @@ static int grow(crgpu_ctx* c, uint8_t** p, size_t* cap, size_t want) {
 static int host_call(crgpu_ctx* c, int codec, crgpu_dict* dict, int decode, const uint8_t* in, const uint64_t* in_off,
                      const uint32_t* in_size, uint32_t nblocks, uint8_t* out, const uint64_t* out_off,
                      const uint32_t* out_cap, uint32_t* out_size, crgpu_models* models = NULL,
-                     crgpu_model_set* set = NULL, const uint32_t* seq_first = NULL, uint32_t nseq = 0, crgpu_decode_set* dset = NULL) {
+                     crgpu_model_set* set = NULL, const uint32_t* seq_first = NULL, uint32_t nseq = 0, crgpu_decode_set* dset = NULL,
+                     crgpu_dict_set* dicts = NULL) {
     if (!c) return CRGPU_E_ARG;
     if (nblocks == 0) return CRGPU_OK;
     if (!in || !in_off || !in_size || !out || !out_off || !out_size || (decode && !out_cap)) return CRGPU_E_ARG;
@@ -2481,7 +2506,7 @@ static int host_call(crgpu_ctx* c, int codec, crgpu_dict* dict, int decode, cons
             room = out_cap[b];
             if (room > max_block) max_block = room;
         } else {
-            room = dict ? in_size[b] + 1u : crgpu_bound(codec, in_size[b]);
+            room = dict || dicts ? in_size[b] + 1u : crgpu_bound(codec, in_size[b]);
             if (in_size[b] > max_block) max_block = in_size[b];
         }
         h_cap[b] = room;
@@ -2515,6 +2540,8 @@ static int host_call(crgpu_ctx* c, int codec, crgpu_dict* dict, int decode, cons
     if (e != hipSuccess) { free(h_in_off); free(h_cap); return fail(c, e, "hipMemcpyAsync(H2D)"); }
     if (dict && decode) rc = crgpu_dict_decode_blocks_dev(c, dict, c->d_in, d_in_off, d_in_size, nblocks, max_block, c->d_out, d_out_off, d_cap, d_out_size, 0);
     else if (dict)      rc = crgpu_dict_encode_blocks_dev(c, dict, c->d_in, d_in_off, d_in_size, nblocks, max_block, c->d_out, d_out_off, d_out_size, 0);
+    else if (dicts && decode) rc = crgpu_dict_decode_sequences_dev(c, dicts, c->d_in, d_in_off, d_in_size, seq_first, nseq, max_block, c->d_out, d_out_off, d_cap, d_out_size, 0);
+    else if (dicts)     rc = crgpu_dict_encode_sequences_dev(c, dicts, c->d_in, d_in_off, d_in_size, seq_first, nseq, max_block, c->d_out, d_out_off, d_out_size, 0);
     else if (dset)      rc = crgpu_decode_sequences_carried_dev(c, codec, dset, c->d_in, d_in_off, d_in_size, seq_first, nseq, c->d_out, d_out_off, d_cap, d_out_size, 0);
     else if (decode)    rc = crgpu_decode_blocks_dev(c, codec, c->d_in, d_in_off, d_in_size, nblocks, max_block, c->d_out, d_out_off, d_cap, d_out_size, 0);
     else if (models)    rc = crgpu_encode_blocks_carried_dev(c, codec, models, c->d_in, d_in_off, d_in_size, nblocks, c->d_out, d_out_off, d_out_size);
@@ -2612,6 +2639,248 @@ extern "C" int crgpu_dict_decode_blocks(crgpu_ctx* c, crgpu_dict* d, const uint8
                                         const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_size) {
     if (!d) return CRGPU_E_ARG;
     return host_call(c, 0, d, 1, in, in_off, in_size, nblocks, out, out_off, out_cap, out_size);
+}
+
+/* ------------------------------------------------------------------ a dictionary per sequence (crgpu_dictset.h) */
+
+struct crgpu_dict_set {
+    crgpu_ctx*    ctx;
+    uint32_t      ndict;
+    int           with_trie;
+    uint32_t*     nwords;                  /* host, per dictionary */
+    uint32_t*     nnodes;
+    uint8_t*      d_words;                 /* words | wlen | word_off | node_off | the CrDict table */
+    uint8_t*      d_trie;                  /* next | ids of all dictionaries */
+    const CrDict* d_tab;
+    uint32_t*     h_map;   size_t h_map_cap;   /* block -> dictionary, as it was uploaded with the last call */
+    uint8_t*      d_map;   size_t map_cap;
+    uint8_t*      d_tmp;   size_t tmp_cap;
+    uint8_t*      d_match; size_t match_cap;
+};
+
+extern "C" void crgpu_dict_set_destroy(crgpu_dict_set* d) {
+    if (!d) return;
+    (void)hipSetDevice(d->ctx->device);
+    (void)hipStreamSynchronize(d->ctx->stream);
+    (void)hipFree(d->d_words); (void)hipFree(d->d_trie); (void)hipFree(d->d_map); (void)hipFree(d->d_tmp); (void)hipFree(d->d_match);
+    free(d->nwords); free(d->nnodes); free(d->h_map);
+    free(d);
+}
+extern "C" int crgpu_dict_set_words(const crgpu_dict_set* d, uint32_t i) { return d && i < d->ndict ? (int)d->nwords[i] : CRGPU_E_ARG; }
+extern "C" int crgpu_dict_set_nodes(const crgpu_dict_set* d, uint32_t i) { return d && i < d->ndict ? (int)d->nnodes[i] : CRGPU_E_ARG; }
+
+/* what crgpu_dict_set_create allocates besides the set itself: released by it whatever happens */
+struct DictSetTemp { uint8_t* h; uint8_t* d_build; uint8_t* d_first; };
+
+static int dict_set_fill(crgpu_ctx* c, crgpu_dict_set* d, const char* const* texts, DictSetTemp& T) {
+    const uint32_t S = d->ndict;
+    /* slots per dictionary: its lines and one for a last line without '\n' */
+    u64 totw = 0;
+    for (uint32_t i = 0; i < S; i++) {
+        u64 lines = 0;
+        for (const char* p = texts[i]; *p; p++) lines += *p == '\n';
+        if (lines > CR_DIC_MAXW) { snprintf(c->err, sizeof c->err, "dictionary %u has more than %u lines", i, CR_DIC_MAXW); return CRGPU_E_ARG; }
+        totw += lines + 1u;
+    }
+    const u64 o_wlen = totw * CR_DIC_WORD_STRIDE, o_woff = align_up(o_wlen + totw, 8), o_noff = align_up(o_woff + 4ull * (S + 1u), 8);
+    const u64 o_tab = o_noff + 8ull * (S + 1u), total = o_tab + sizeof(CrDict) * (u64)S;
+    if (hipHostMalloc((void**)&T.h, (size_t)total, hipHostMallocDefault) != hipSuccess) { T.h = NULL; return CRGPU_E_NOMEM; }
+    memset(T.h, 0, (size_t)total);
+    uint32_t* word_off = (uint32_t*)(T.h + o_woff);
+    u64* node_off = (u64*)(T.h + o_noff);
+    CrDict* tab = (CrDict*)(T.h + o_tab);
+    uint32_t max_words = 0;
+    for (uint32_t i = 0; i < S; i++) {
+        uint32_t nw = 0;
+        if (dict_parse(texts[i], T.h + (u64)word_off[i] * CR_DIC_WORD_STRIDE, T.h + o_wlen + word_off[i], &nw) != CRGPU_OK) {
+            snprintf(c->err, sizeof c->err, "dictionary %u has more than %u lines", i, CR_DIC_MAXW);
+            return CRGPU_E_ARG;
+        }
+        d->nwords[i] = nw;
+        word_off[i + 1u] = word_off[i] + nw + 1u;
+        if (nw > max_words) max_words = nw;
+    }
+    if (hipMalloc((void**)&d->d_words, (size_t)total) != hipSuccess) { d->d_words = NULL; return CRGPU_E_NOMEM; }
+    CR_TRY(c, hipMemcpyAsync(d->d_words, T.h, (size_t)o_noff, hipMemcpyHostToDevice, c->stream));      /* words, lengths, word_off: one copy */
+    u64 nodes = 0;
+    if (d->with_trie) {
+        const u64 b_o1 = align_up(2u * totw, 8), b_base = align_up(b_o1 + 2u * totw, 8), b_lcp = b_base + 4u * totw, b_nn = align_up(b_lcp + totw, 8);
+        if (hipMalloc((void**)&T.d_build, (size_t)(b_nn + 4ull * S)) != hipSuccess) { T.d_build = NULL; return CRGPU_E_NOMEM; }
+        CrDictSetBuild P; memset(&P, 0, sizeof P);
+        P.words = d->d_words; P.wlen = d->d_words + o_wlen; P.word_off = (const uint32_t*)(d->d_words + o_woff); P.ndict = S;
+        P.order0 = (uint16_t*)T.d_build; P.order1 = (uint16_t*)(T.d_build + b_o1); P.base = (uint32_t*)(T.d_build + b_base);
+        P.lcp = T.d_build + b_lcp; P.nnodes = (uint32_t*)(T.d_build + b_nn);
+        CR_CARRY_RC(carry_group_open(c));
+        CR_CARRY_STAGE("k_dset_sort", crds_launch_sort(c->stream, P));
+        CR_CARRY_RC(carry_group_close(c));
+        CR_TRY(c, hipMemcpyAsync(d->nnodes, P.nnodes, 4u * (size_t)S, hipMemcpyDeviceToHost, c->stream));      /* the one readback: it sizes the tries */
+        CR_TRY(c, hipStreamSynchronize(c->stream));
+        uint32_t max_nodes = 0;
+        for (uint32_t i = 0; i < S; i++) { node_off[i] = nodes; nodes += d->nnodes[i]; if (d->nnodes[i] > max_nodes) max_nodes = d->nnodes[i]; }
+        node_off[S] = nodes;
+        if (hipMalloc((void**)&d->d_trie, (size_t)(nodes * (512u + 4u))) != hipSuccess) { d->d_trie = NULL; snprintf(c->err, sizeof c->err, "hipMalloc(%llu) for %llu trie nodes failed", nodes * 516ull, nodes); return CRGPU_E_NOMEM; }
+        if (hipMalloc((void**)&T.d_first, (size_t)(nodes * 4u)) != hipSuccess) { T.d_first = NULL; return CRGPU_E_NOMEM; }
+        P.node_off = (const u64*)(d->d_words + o_noff);
+        P.next = (uint32_t*)d->d_trie; P.ids = (int32_t*)(d->d_trie + nodes * 512u); P.first = (int32_t*)T.d_first;
+        CR_TRY(c, hipMemsetAsync(P.next, 0, (size_t)(nodes * 512u), c->stream));
+        CR_TRY(c, hipMemsetAsync(P.ids, 0xFF, (size_t)(nodes * 4u), c->stream));          /* -1: no word ends here */
+        CR_TRY(c, hipMemsetAsync(P.first, 0x7F, (size_t)(nodes * 4u), c->stream));        /* above every word number */
+        CR_TRY(c, hipMemcpyAsync(d->d_words + o_noff, T.h + o_noff, 8u * ((size_t)S + 1u), hipMemcpyHostToDevice, c->stream));
+        uint32_t rows_grid = (max_nodes + 3u) / 4u;
+        if (rows_grid > (uint32_t)c->num_cu * 8u) rows_grid = (uint32_t)c->num_cu * 8u;
+        CR_CARRY_RC(carry_group_open(c));
+        CR_CARRY_STAGE("k_dset_link", crds_launch_link(c->stream, P));
+        if (max_words) CR_CARRY_STAGE("k_dset_mark", crds_launch_mark(c->stream, P, max_words));
+        CR_CARRY_STAGE("k_dset_ids", crds_launch_ids(c->stream, P, rows_grid));
+        CR_CARRY_STAGE("k_dset_finish", crds_launch_finish(c->stream, P, rows_grid));
+        CR_CARRY_RC(carry_group_close(c));
+    }
+    for (uint32_t i = 0; i < S; i++) {
+        CrDict& D = tab[i];
+        if (d->with_trie) { D.next = (const uint32_t*)d->d_trie + node_off[i] * 128u; D.ids = (const int32_t*)(d->d_trie + nodes * 512u) + node_off[i]; }
+        D.words = d->d_words + (u64)word_off[i] * CR_DIC_WORD_STRIDE; D.wlen = d->d_words + o_wlen + word_off[i];
+        D.nwords = d->nwords[i];
+        D.level1 = (uint32_t)((65535 - (int)d->nwords[i]) / 255 - 1);             /* cr-diccode.h:40 */
+    }
+    d->d_tab = (const CrDict*)(d->d_words + o_tab);
+    CR_TRY(c, hipMemcpyAsync(d->d_words + o_tab, T.h + o_tab, sizeof(CrDict) * (size_t)S, hipMemcpyHostToDevice, c->stream));
+    CR_TRY(c, hipStreamSynchronize(c->stream));
+    return CRGPU_OK;
+}
+
+extern "C" int crgpu_dict_set_create(crgpu_ctx* c, const char* const* texts, uint32_t ndict, int with_trie, crgpu_dict_set** out) {
+    if (!c || !texts || !out) return CRGPU_E_ARG;
+    *out = NULL;
+    if (ndict == 0 || ndict > 65535u) { snprintf(c->err, sizeof c->err, "a dictionary set holds 1 .. 65535 dictionaries (%u)", ndict); return CRGPU_E_ARG; }
+    for (uint32_t i = 0; i < ndict; i++) if (!texts[i]) return CRGPU_E_ARG;
+    CR_TRY(c, hipSetDevice(c->device));
+    crgpu_dict_set* d = (crgpu_dict_set*)calloc(1, sizeof *d);
+    if (!d) return CRGPU_E_NOMEM;
+    d->ctx = c; d->ndict = ndict; d->with_trie = with_trie != 0;
+    d->nwords = (uint32_t*)calloc(ndict, sizeof(uint32_t));
+    d->nnodes = (uint32_t*)calloc(ndict, sizeof(uint32_t));
+    DictSetTemp T = {NULL, NULL, NULL};
+    const int rc = d->nwords && d->nnodes ? dict_set_fill(c, d, texts, T) : CRGPU_E_NOMEM;
+    if (rc != CRGPU_OK) (void)hipStreamSynchronize(c->stream);                     /* (nothing in flight reads what is released now) */
+    (void)hipFree(T.d_build); (void)hipFree(T.d_first);
+    if (T.h) (void)hipHostFree(T.h);
+    if (rc != CRGPU_OK) { crgpu_dict_set_destroy(d); return rc; }
+    *out = d;
+    return CRGPU_OK;
+}
+
+/* the refusals of a stage call on a set, before anything is staged or launched */
+static int dict_set_check(crgpu_ctx* c, const crgpu_dict_set* d, int decode, const uint32_t* seq_first, uint32_t nseq) {
+    if (!c || !d || d->ctx != c) return CRGPU_E_ARG;
+    if (nseq > d->ndict) { snprintf(c->err, sizeof c->err, "%u sequences for a set of %u dictionaries", nseq, d->ndict); return CRGPU_E_ARG; }
+    if (!decode && !d->with_trie) { snprintf(c->err, sizeof c->err, "the dictionary set was made without tries: it decodes only"); return CRGPU_E_ARG; }
+    if (nseq && !seq_first) return CRGPU_E_ARG;
+    for (uint32_t s = 0; s < nseq; s++) if (seq_first[s + 1u] < seq_first[s]) { snprintf(c->err, sizeof c->err, "seq_first descends at sequence %u", s); return CRGPU_E_ARG; }
+    return CRGPU_OK;
+}
+
+static int dict_set_launch(crgpu_ctx* c, crgpu_dict_set* d, int decode, CrBatch& B, const uint32_t* seq_first, uint32_t nseq,
+                           uint32_t max_block, int sync) {
+    CR_CARRY_RC(dict_set_check(c, d, decode, seq_first, nseq));
+    if (max_block > CRGPU_MAX_BLOCK + 1u) return CRGPU_E_ARG;
+    const uint32_t first = nseq ? seq_first[0] : 0u, nblocks = nseq ? seq_first[nseq] - first : 0u;
+    if (nblocks == 0) return CRGPU_OK;
+    if (!B.in || !B.in_off || !B.in_size || !B.out || !B.out_off || !B.out_size || (decode && !B.out_cap)) return CRGPU_E_ARG;
+    CR_TRY(c, hipSetDevice(c->device));
+    B.in_off += first; B.in_size += first; B.out_off += first; B.out_size += first; B.nblocks = nblocks;
+    if (decode) B.out_cap += first;
+    /* the block -> dictionary map travels with the call */
+    if (d->h_map_cap < nblocks) {
+        uint32_t* nm = (uint32_t*)realloc(d->h_map, sizeof(uint32_t) * (size_t)nblocks);
+        if (!nm) return CRGPU_E_NOMEM;
+        d->h_map = nm; d->h_map_cap = nblocks;
+    }
+    for (uint32_t s = 0; s < nseq; s++) for (uint32_t b = seq_first[s]; b < seq_first[s + 1u]; b++) d->h_map[b - first] = s;
+    CR_CARRY_RC(grow(c, &d->d_map, &d->map_cap, 4u * (size_t)nblocks));
+    CR_TRY(c, hipMemcpyAsync(d->d_map, d->h_map, 4u * (size_t)nblocks, hipMemcpyHostToDevice, c->stream));
+    uint32_t grid = (uint32_t)c->num_cu * 16u;
+    if (grid > nblocks) grid = nblocks;
+    CrDictBatch DB; memset(&DB, 0, sizeof DB);
+    DB.set = d->d_tab; DB.block_dict = (const uint32_t*)d->d_map;
+    if (!decode) {
+        DB.tmp_stride = align_up((u64)max_block * 3u + 64u * (max_block / 2000000u + 2u), 256);        /* as dict_launch */
+        CR_CARRY_RC(grow(c, &d->d_tmp, &d->tmp_cap, (size_t)(DB.tmp_stride * grid)));
+        DB.tmp = d->d_tmp;
+        DB.max_block = max_block;
+        DB.match_stride = align_up((u64)(max_block ? max_block : 1u), 64);
+        CR_CARRY_RC(grow(c, &d->d_match, &d->match_cap, (size_t)(DB.match_stride * 4u * nblocks)));
+        DB.match = (uint32_t*)d->d_match;
+    }
+    B.ticket = c->ticket;
+    CR_TRY(c, hipMemsetAsync(c->ticket, 0, 8, c->stream));
+    CR_CARRY_RC(carry_group_open(c));
+    CR_TRY(c, hipEventRecord(c->ev0, c->stream));
+    if (decode) {
+        CR_CARRY_STAGE("k_dict_decode", hipLaunchKernelGGL(k_dict_decode<true>, CR_G(k_dict_decode<true>, CRGPU_WAVE, 0), dim3(CRGPU_WAVE), 0, c->stream, B, DB));
+    } else {
+        const uint32_t chunks = (max_block + CR_DM_CHUNK - 1u) / CR_DM_CHUNK;
+        CR_CARRY_STAGE("k_dict_match", hipLaunchKernelGGL(k_dict_match<true>, dim3(nblocks, chunks ? chunks : 1u), dim3(256), 0, c->stream, B, DB));
+        CR_CARRY_STAGE("k_dict_encode", hipLaunchKernelGGL(k_dict_encode<true>, CR_G(k_dict_encode<true>, CRGPU_WAVE, 0), dim3(CRGPU_WAVE), 0, c->stream, B, DB));
+    }
+    CR_TRY(c, hipEventRecord(c->ev_stage[c->n_stages], c->stream));
+    CR_TRY(c, hipEventRecord(c->ev_mid, c->stream));
+    CR_TRY(c, hipEventRecord(c->ev1, c->stream));
+    c->timed = 1;
+    CR_CARRY_RC(stage_end(c));
+    if (!sync) return CRGPU_OK;
+    if (!decode) { CR_TRY(c, hipStreamSynchronize(c->stream)); return CRGPU_OK; }
+    uint32_t* sizes = (uint32_t*)malloc(sizeof(uint32_t) * (size_t)nblocks);
+    if (!sizes) return CRGPU_E_NOMEM;
+    hipError_t e = hipMemcpyAsync(sizes, B.out_size, 4u * (size_t)nblocks, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    uint32_t failed = 0;
+    for (uint32_t b = 0; b < nblocks && e == hipSuccess; b++) failed += sizes[b] == 0xFFFFFFFFu;
+    free(sizes);
+    if (e != hipSuccess) return fail(c, e, "reading the decoded sizes");
+    if (failed) { snprintf(c->err, sizeof c->err, "%u blocks could not be decoded (out_size 0xFFFFFFFF)", failed); return CRGPU_E_CORRUPT; }
+    return CRGPU_OK;
+}
+
+extern "C" int crgpu_dict_encode_sequences_dev(crgpu_ctx* c, crgpu_dict_set* d, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_size,
+                                               const uint32_t* seq_first, uint32_t nseq, uint32_t max_block,
+                                               uint8_t* out, const uint64_t* out_off, uint32_t* out_size, int sync) {
+    if (!c || !d) return CRGPU_E_ARG;
+    CrBatch B; memset(&B, 0, sizeof B);
+    B.in = in; B.in_off = (const u64*)in_off; B.in_size = in_size; B.out = out; B.out_off = (const u64*)out_off; B.out_size = out_size;
+    return dict_set_launch(c, d, 0, B, seq_first, nseq, max_block, sync);
+}
+extern "C" int crgpu_dict_decode_sequences_dev(crgpu_ctx* c, crgpu_dict_set* d, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_size,
+                                               const uint32_t* seq_first, uint32_t nseq, uint32_t max_block,
+                                               uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_size, int sync) {
+    if (!c || !d) return CRGPU_E_ARG;
+    CrBatch B; memset(&B, 0, sizeof B);
+    B.in = in; B.in_off = (const u64*)in_off; B.in_size = in_size; B.out = out; B.out_off = (const u64*)out_off; B.out_cap = out_cap; B.out_size = out_size;
+    return dict_set_launch(c, d, 1, B, seq_first, nseq, max_block, sync);
+}
+
+/* HOST pointers: the blocks seq_first[0] .. seq_first[nseq] - 1 are packed on the device as crgpu_dict_encode_blocks packs them */
+static int dict_set_host(crgpu_ctx* c, crgpu_dict_set* d, int decode, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_size,
+                         const uint32_t* seq_first, uint32_t nseq, uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_size) {
+    CR_CARRY_RC(dict_set_check(c, d, decode, seq_first, nseq));                                   /* (the refusals hold for an empty call too) */
+    uint32_t* rel = (uint32_t*)malloc(sizeof(uint32_t) * ((size_t)nseq + 1u));
+    if (!rel) return CRGPU_E_NOMEM;
+    const uint32_t first = nseq ? seq_first[0] : 0u;
+    rel[0] = 0;
+    for (uint32_t s = 1; s <= nseq; s++) rel[s] = seq_first[s] - first;
+    const int rc = rel[nseq] == 0 ? CRGPU_OK
+                                  : host_call(c, 0, NULL, decode, in, in_off ? in_off + first : NULL, in_size ? in_size + first : NULL, rel[nseq], out,
+                                              out_off ? out_off + first : NULL, out_cap ? out_cap + first : NULL, out_size ? out_size + first : NULL,
+                                              NULL, NULL, rel, nseq, NULL, d);
+    free(rel);
+    return rc;
+}
+extern "C" int crgpu_dict_encode_sequences(crgpu_ctx* c, crgpu_dict_set* d, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_size,
+                                           const uint32_t* seq_first, uint32_t nseq, uint8_t* out, const uint64_t* out_off, uint32_t* out_size) {
+    return dict_set_host(c, d, 0, in, in_off, in_size, seq_first, nseq, out, out_off, NULL, out_size);
+}
+extern "C" int crgpu_dict_decode_sequences(crgpu_ctx* c, crgpu_dict_set* d, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_size,
+                                           const uint32_t* seq_first, uint32_t nseq, uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_size) {
+    return dict_set_host(c, d, 1, in, in_off, in_size, seq_first, nseq, out, out_off, out_cap, out_size);
 }
 
 /* ------------------------------------------------------------------ dictionary pick on the device (crgpu_dicpick.h) */

@@ -309,6 +309,44 @@ int crgpu_dict_decode_blocks(crgpu_ctx* ctx, crgpu_dict* dict,
                              uint32_t nblocks, uint8_t* out, const uint64_t* out_off,
                              const uint32_t* out_cap, uint32_t* out_size);
 
+/* ---- a dictionary per sequence of blocks (many files at once) ---------------------------------
+ * crgpu_dict_set: ndict dictionaries made in one call, their tries built ON THE DEVICE (csrc/crgpu_dictset.h): the host only
+ * parses the lines, the words of all dictionaries go up in one copy, and the node counts come back once to size the tries.
+ * Device memory per dictionary: nodes x (512 + 4) bytes of trie (~40 MB for a dictionary of 25 000 words) plus
+ * (words + 1) x 25 bytes of words; without a trie the words alone. The set also owns the encode scratch of its calls.
+ *   texts[i]: dictionary text as dicpick() writes it (one word per line, NUL-terminated). with_trie = 0: words only, as
+ *   dictionary_load(text, 0): such a set decodes and refuses to encode.
+ * The stage calls give sequence s of blocks dictionary s of the set, all sequences in one launch per kernel. Pointer
+ * conventions of crgpu_dict_encode_blocks_dev / _decode_blocks_dev; seq_first: HOST memory, nseq + 1 entries, ascending;
+ * sequence s owns blocks seq_first[s] .. seq_first[s+1]-1 of the flat block arrays (it may own none). Coded bytes are those of
+ * crgpu_dict_*_blocks with the sequence's dictionary; decode failures as there (0xFFFFFFFF per bad block, CRGPU_E_CORRUPT
+ * when sync). The variants without _dev take HOST pointers and stage as crgpu_dict_encode_blocks / _decode_blocks do.
+ * CRGPU_E_ARG: ndict == 0, a text of more than 25 000 lines, i >= ndict (_words / _nodes return it), nseq above the set's
+ * size, a descending seq_first, a set of another context, an encode call on a set made without tries,
+ * max_block > CRGPU_MAX_BLOCK + 1. */
+typedef struct crgpu_dict_set crgpu_dict_set;
+int  crgpu_dict_set_create(crgpu_ctx* ctx, const char* const* texts, uint32_t ndict, int with_trie, crgpu_dict_set** out);
+void crgpu_dict_set_destroy(crgpu_dict_set* set);
+int  crgpu_dict_set_words(const crgpu_dict_set* set, uint32_t i);   /* dictionary_load's return value for texts[i]  */
+int  crgpu_dict_set_nodes(const crgpu_dict_set* set, uint32_t i);   /* trie nodes incl. the root; 0 without a trie */
+int crgpu_dict_encode_sequences_dev(crgpu_ctx* ctx, crgpu_dict_set* set,
+                                    const uint8_t* in, const uint64_t* in_off, const uint32_t* in_size,
+                                    const uint32_t* seq_first, uint32_t nseq, uint32_t max_block,
+                                    uint8_t* out, const uint64_t* out_off, uint32_t* out_size, int sync);
+int crgpu_dict_decode_sequences_dev(crgpu_ctx* ctx, crgpu_dict_set* set,
+                                    const uint8_t* in, const uint64_t* in_off, const uint32_t* in_size,
+                                    const uint32_t* seq_first, uint32_t nseq, uint32_t max_block,
+                                    uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
+                                    uint32_t* out_size, int sync);
+int crgpu_dict_encode_sequences(crgpu_ctx* ctx, crgpu_dict_set* set,
+                                const uint8_t* in, const uint64_t* in_off, const uint32_t* in_size,
+                                const uint32_t* seq_first, uint32_t nseq,
+                                uint8_t* out, const uint64_t* out_off, uint32_t* out_size);
+int crgpu_dict_decode_sequences(crgpu_ctx* ctx, crgpu_dict_set* set,
+                                const uint8_t* in, const uint64_t* in_off, const uint32_t* in_size,
+                                const uint32_t* seq_first, uint32_t nseq,
+                                uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_size);
+
 /* ---- several GPUs of one node (csrc/crgpu_multi.hip) -------------------------------------------------
  * The block loop of src/main.c:174-206 (encode) / :263-292 (decode) for INDEPENDENT datablocks, sharded over G devices:
  * one host thread, context and stream per device; rank r codes the contiguous block range [r*ceil(n/G), (r+1)*ceil(n/G));
